@@ -13,7 +13,14 @@ Run directly (N=1) or under torch.distributed.run with one rank per GPU:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
       --master-addr 127.0.0.1 bench.py --gpus 8 --steps 1000 --warmup 100
 
-Rank 0 prints ONE JSON line with the whole-job metric.
+Rank 0 prints ONE JSON line with the whole-job metric. A plain run does
+nothing besides set-up, warm-up and the timed steps; --full is where any
+measurement that does not feed that line belongs (none exists yet).
+
+--dump-outputs DIR writes what the last timed step left its caller (the
+updated parameters and the step's loss) to DIR/<name>.npy, float32. The
+inputs are seeded, so two builds run with the same arguments can be
+compared array for array.
 
 Extra workloads (same PS machinery): --workload nmf (sparse-embedding
 2-ps-shard NMF config), --workload inception (conv net, bf16).
@@ -32,6 +39,56 @@ import torch.distributed as dist
 def log(msg):
     sys.stderr.write(msg + "\n")
     sys.stderr.flush()
+
+
+# --dump-outputs writes at most this many bytes of array data in all
+# (under 64 MB by either count, with room for the .npy headers)
+DUMP_BUDGET = 60 * 1000 * 1000
+
+
+def graphed(step, last):
+    """GraphedStep(step) that also notes which tensor the capture run
+    stored in last["out"]: a replay rewrites that tensor in place, so
+    while the graph is kept it, not the last eager result, holds the
+    step's loss. The tracing wrapper is only in the way during
+    GraphedStep's own set-up; afterwards eager calls go straight to
+    ``step`` again."""
+    from tfmesos_amd.utils.graphstep import GraphedStep
+
+    def tracing():
+        step()
+        if torch.cuda.is_current_stream_capturing():
+            last["captured"] = last["out"]
+
+    g = GraphedStep(tracing)
+    g.fn = step
+    return g
+
+
+def last_result(one_step, last):
+    if getattr(one_step, "graph", None) is not None:
+        return last["captured"]
+    return last["out"]
+
+
+def dump_outputs(dirname, arrays):
+    """Write name -> tensor as DIR/<name>.npy (float32; float64 kept).
+    An array over its share of DUMP_BUDGET is cut down to a fixed,
+    seeded sample of its flattened elements."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(arrays))
+    for name, t in sorted(arrays.items()):
+        t = torch.as_tensor(t).detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        a = t.cpu().numpy()
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.random.RandomState(0).choice(a.size, keep, replace=False)
+            idx.sort()
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def run_mnist(args, device, rank, world):
@@ -55,6 +112,7 @@ def run_mnist(args, device, rank, world):
 
     pview = (lambda n: trainer.store.view(n, bf16=True)) \
         if act_dtype == torch.bfloat16 else (lambda n: trainer.store.view(n))
+    last = {"out": None}   # the step's loss, for --dump-outputs
 
     if world == 1 and device.type == "cuda" and not args.no_fuse \
             and model.supports_fused_apply(trainer, x):
@@ -62,18 +120,26 @@ def run_mnist(args, device, rank, world):
         # kernels' epilogues (4 launches/step instead of 5) — same
         # update math, measured not skipped
         def one_step():
-            model.fwd_bwd_apply(trainer, x, y, lr=args.lr)
+            last["out"] = model.fwd_bwd_apply(trainer, x, y, lr=args.lr)
     else:
         def one_step():
             if roles.is_worker:
-                model.fwd_bwd(pview, x, y, trainer.grad_view)
+                last["out"] = model.fwd_bwd(pview, x, y, trainer.grad_view)
             trainer.step()
 
     if world == 1 and device.type == "cuda" and not args.no_graph:
         # single-GPU hot path: capture the whole 8-kernel step as ONE
         # hipGraph replay (no collectives inside)
-        from tfmesos_amd.utils.graphstep import GraphedStep
-        one_step = GraphedStep(one_step)
+        one_step = graphed(one_step, last)
+
+    def outputs():
+        # collective: every rank ends up with all shards' fp32 masters
+        trainer.sync_masters()
+        out = {n: trainer.store.view(n) for n, _ in model.param_specs()}
+        if roles.is_worker:
+            out["loss"] = last_result(one_step, last)
+        return out
+    one_step.outputs = outputs
 
     return one_step, {
         "model": "mnist_replica_mlp_784x%dx10" % args.hidden,
@@ -106,6 +172,15 @@ def run_nmf(args, device, rank, world):
     def one_step():
         wl.one_step()
     one_step.finalize = getattr(wl, "finalize", lambda: None)
+
+    def outputs():
+        if world == 1:
+            return {"W": wl.W, "H": wl.H}
+        # sparse PS: this rank's factor tables, or the worker's loss
+        if wl.is_ps:
+            return {n: t.master for n, t in wl.server.tables.items()}
+        return {"loss": torch.tensor(wl.losses[-1:])}
+    one_step.outputs = outputs
     return one_step, {
         "model": "nmf_%dx%d_rank%d" % (args.nmf_n, args.nmf_n, args.nmf_rank),
         "global_batch": gbatch,
@@ -133,12 +208,14 @@ def run_inception(args, device, rank, world):
     x, y = synthetic_images(args.inc_batch, size=args.inc_size,
                             classes=args.classes, device=device,
                             dtype=torch.bfloat16, seed=1000 + rank)
+    last = {"out": None}   # the step's loss, for --dump-outputs
 
     def one_step():
         if trainer.roles.is_worker:
             trainer.zero_grad()
             loss = ops.softmax_xent_loss(model(x).contiguous(), y)
             loss.backward()
+            last["out"] = loss.detach()
         trainer.step()
 
     if world == 1 and device.type == "cuda" and not args.no_graph:
@@ -147,10 +224,16 @@ def run_inception(args, device, rank, world):
         # replay doesn't clearly win, and we fall back if any captured
         # op refuses graph capture
         try:
-            from tfmesos_amd.utils.graphstep import GraphedStep
-            one_step = GraphedStep(one_step)
+            one_step = graphed(one_step, last)
         except Exception as e:
             log("graph capture unavailable, running eager: %r" % (e,))
+
+    def outputs():
+        out = {"params": trainer.t.sync_masters()}
+        if trainer.roles.is_worker:
+            out["loss"] = last_result(one_step, last)
+        return out
+    one_step.outputs = outputs
 
     return one_step, {
         "model": "inception_v3_%d" % args.inc_size,
@@ -185,6 +268,12 @@ def main():
     p.add_argument("--inc-batch", type=int, default=32)
     p.add_argument("--inc-size", type=int, default=299)
     p.add_argument("--classes", type=int, default=1000)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step "
+                        "produced to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline "
+                        "figure (there is none yet: same as a plain run)")
     args = p.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -225,6 +314,13 @@ def main():
                          device=device if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs:
+        arrays = one_step.outputs()
+        if device.type == "cuda":
+            torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
 
     if rank == 0:
         steps_per_sec = args.steps / elapsed

@@ -40,6 +40,11 @@ def _spawn_bench_nmf(world, steps=8):
             "RANK": str(rank), "WORLD_SIZE": str(world),
             "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port),
             "PYTHONPATH": REPO,
+            # CPU + gloo is what these tests cover, also on a box with
+            # a GPU (there the ranks would all pick RCCL on one device,
+            # which RCCL refuses; the on-GPU variant is in
+            # test_e2e_gpu.py)
+            "HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1",
         })
         procs.append(subprocess.Popen(
             [sys.executable, os.path.join(REPO, "bench.py"),
@@ -47,10 +52,16 @@ def _spawn_bench_nmf(world, steps=8):
              "--nmf-n", "300", "--nmf-rank", "32", "--nmf-batch", "64"],
             env=env, stdout=subprocess.PIPE, text=True))
     outs = []
-    for p in procs:
-        out, _ = p.communicate(timeout=180)
-        assert p.returncode == 0, out
-        outs.append(out)
+    try:
+        for p in procs:
+            out, _ = p.communicate(timeout=180)
+            assert p.returncode == 0, out
+            outs.append(out)
+    finally:
+        # a rank that died must not leave its peers waiting behind
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
     return outs
 
 

@@ -20,7 +20,9 @@ def test_step_timer_counts_and_reports():
     assert len(lines) == 2 and lines[0].startswith("w0 step 10")
 
 
-def test_graphed_step_cpu_fallback_runs_eagerly():
+def test_graphed_step_cpu_fallback_runs_eagerly(monkeypatch):
+    # the CPU fallback is what is under test, also on a box with a GPU
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     calls = []
     g = GraphedStep(lambda: calls.append(1))
     assert g.graph is None          # no GPU here
