@@ -79,10 +79,13 @@ class SparseNMF(object):
     each worker step pulls only the minibatch's factor rows, computes
     the minibatch Frobenius gradient on MFMA GEMMs, and pushes sparse
     row grads back (HIP gather/scatter-add on a GPU PS).
+    ``optimizer`` / ``opt_hparams`` select the tables' sparse optimizer
+    (EmbeddingTable: sgd, adagrad, adam); the default is plain SGD.
     """
 
     def __init__(self, rank, world, device="cpu", n=1000, factor_rank=200,
-                 batch=256, lr=0.05, seed=0):
+                 batch=256, lr=0.05, seed=0, optimizer="sgd",
+                 opt_hparams=None):
         from tfmesos_amd.ps.replica import init_distributed
         init_distributed(device)
         from tfmesos_amd.ps.sparse import (
@@ -116,7 +119,8 @@ class SparseNMF(object):
                 if home == rank:
                     tables.append(EmbeddingTable(
                         name, n, factor_rank, device=device, lr=lr,
-                        seed=seed + hash(name) % 1000))
+                        seed=seed + hash(name) % 1000,
+                        optimizer=optimizer, **(opt_hparams or {})))
             self.server = SparsePSServer(rank, tables, worker_ranks, groups)
             import threading
             self._srv_thread = threading.Thread(target=self.server.serve,

@@ -10,7 +10,9 @@ numerics tests compare HIP kernel output against these references.
 Op inventory mirrors what the reference delegated to TensorFlow's PS
 runtime: fused optimizer apply (SGD/momentum, Adagrad,
 Adam), bf16 GEMM with fused bias+ReLU epilogue, fused softmax
-cross-entropy, embedding gather / scatter-add.
+cross-entropy, embedding gather / scatter-add, fused sparse optimizer
+apply for embedding rows (sparse_sgd / sparse_adagrad / sparse_adam —
+TF's SparseApply*: duplicates summed, one update per touched row).
 """
 
 import torch
@@ -326,6 +328,109 @@ def embedding_scatter_add(table, ids, rows):
         _ext().embedding_scatter_add(table, ids, rows)
         return
     table.index_add_(0, ids, rows.to(table.dtype))
+
+
+# ------------------------------------------------- sparse optimizer applies
+#
+# TF SparseApply* semantics: per touched row r the summed gradient is
+# G = grad_scale * sum_{i: ids[i]==r} grads[i] (+ weight_decay * p), then
+# the dense per-element formula runs ONCE on that row; ids outside [0, V)
+# are ignored; untouched rows (and their state) never move. GPU: one fused
+# HIP pass over master + state + bf16 shadow (csrc/sparse_apply.hip), no
+# float atomics, bit-reproducible, no host sync.
+
+_SPARSE_SGD, _SPARSE_SGD_MOM, _SPARSE_ADAGRAD, _SPARSE_ADAM = 0, 1, 2, 3
+
+
+def _sparse_hip(code, param, ids, grads, s1, s2, bf16_out, step, lr, beta1,
+                beta2, eps, weight_decay, grad_scale):
+    dev = param.device
+    ef = torch.empty(0, device=dev)
+    _ext().sparse_apply(
+        param, ids, grads, s1 if s1 is not None else ef,
+        s2 if s2 is not None else ef,
+        bf16_out if bf16_out is not None
+        else torch.empty(0, dtype=torch.bfloat16, device=dev),
+        code, int(step), float(lr), float(beta1), float(beta2), float(eps),
+        float(weight_decay), float(grad_scale))
+
+
+def _sparse_cpu(param, ids, grads, states, bf16_out, dense_step):
+    """CPU reference: drop out-of-range ids, sum duplicates (unique +
+    index_add_), run the dense CPU formula on the gathered rows and
+    scatter them back. dense_step(p, G, *state_rows) updates in place."""
+    keep = (ids >= 0) & (ids < param.shape[0])
+    ids = ids[keep]
+    if ids.numel() == 0:
+        return
+    uniq, inv = torch.unique(ids, return_inverse=True)
+    G = torch.zeros(uniq.numel(), param.shape[1])
+    G.index_add_(0, inv, grads[keep].float())
+    p = param.index_select(0, uniq)
+    rows = [s.index_select(0, uniq) for s in states]
+    dense_step(p, G, *rows)
+    param.index_copy_(0, uniq, p)
+    for s, r in zip(states, rows):
+        s.index_copy_(0, uniq, r)
+    if bf16_out is not None:
+        bf16_out.index_copy_(0, uniq, p.to(torch.bfloat16))
+
+
+@torch.no_grad()
+def sparse_sgd(param, ids, grads, lr, momentum=0.0, momentum_buf=None,
+               weight_decay=0.0, bf16_out=None, grad_scale=1.0):
+    """Sparse SGD(+momentum, +wd) on the rows ``ids`` of an fp32 [V,D]
+    master; grads [n,D] bf16 or fp32. bf16_out ([V,D] shadow) gets the
+    touched rows refreshed in the same pass."""
+    if momentum and momentum_buf is None:
+        raise ValueError("sparse_sgd: momentum needs a momentum_buf")
+    if not momentum:
+        momentum_buf = None
+    if param.is_cuda:
+        _sparse_hip(_SPARSE_SGD_MOM if momentum else _SPARSE_SGD, param, ids,
+                    grads, momentum_buf, None, bf16_out, 1, lr, momentum, 0.0,
+                    0.0, weight_decay, grad_scale)
+        return
+
+    def step(p, g, *mb):
+        fused_sgd(p, g, lr, momentum=momentum, weight_decay=weight_decay,
+                  momentum_buf=mb[0] if mb else None, grad_scale=grad_scale)
+    _sparse_cpu(param, ids, grads,
+                [momentum_buf] if momentum else [], bf16_out, step)
+
+
+@torch.no_grad()
+def sparse_adagrad(param, ids, grads, accum, lr, eps=1e-10,
+                   weight_decay=0.0, bf16_out=None, grad_scale=1.0):
+    """Sparse Adagrad: a += G^2; p -= lr*G/(sqrt(a)+eps) per touched row
+    (ids [3,3] with grads g,-g leave row and accumulator untouched)."""
+    if param.is_cuda:
+        _sparse_hip(_SPARSE_ADAGRAD, param, ids, grads, accum, None,
+                    bf16_out, 1, lr, 0.0, 0.0, eps, weight_decay, grad_scale)
+        return
+
+    def step(p, g, a):
+        fused_adagrad(p, g, a, lr, eps=eps, weight_decay=weight_decay,
+                      grad_scale=grad_scale)
+    _sparse_cpu(param, ids, grads, [accum], bf16_out, step)
+
+
+@torch.no_grad()
+def sparse_adam(param, ids, grads, exp_avg, exp_avg_sq, step, lr,
+                beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+                bf16_out=None, grad_scale=1.0):
+    """Lazy sparse Adam: only touched rows (and their m, v) move; the
+    bias corrections come from ``step`` (>= 1)."""
+    if param.is_cuda:
+        _sparse_hip(_SPARSE_ADAM, param, ids, grads, exp_avg, exp_avg_sq,
+                    bf16_out, step, lr, beta1, beta2, eps, weight_decay,
+                    grad_scale)
+        return
+
+    def dense(p, g, m, v):
+        fused_adam(p, g, m, v, step, lr, beta1=beta1, beta2=beta2, eps=eps,
+                   weight_decay=weight_decay, grad_scale=grad_scale)
+    _sparse_cpu(param, ids, grads, [exp_avg, exp_avg_sq], bf16_out, dense)
 
 
 # --------------------------------------------------------------- relu bwd

@@ -6,6 +6,7 @@
 #include <hip/hip_bf16.h>
 
 #include "common.h"
+#include "sparse_apply.h"
 
 
 // launchers from the .hip translation units
@@ -746,6 +747,72 @@ void embedding_scatter_add(torch::Tensor table, torch::Tensor ids,
                            rows.data_ptr<float>(), n, D, V, cur_stream());
 }
 
+// Fused sparse optimizer apply (sparse_apply.hip): duplicates summed,
+// then ONE optimizer step per touched row, master + state + bf16 shadow
+// in the same pass. The stable sort of the ids is the inverted index
+// (plumbing; stays on the device, no host sync); everything after it is
+// our HIP. state1/state2/shadow: pass empty tensors when unused.
+void sparse_apply(torch::Tensor table, torch::Tensor ids, torch::Tensor grads,
+                  torch::Tensor state1, torch::Tensor state2,
+                  torch::Tensor shadow, long opt, long step, double lr,
+                  double beta1, double beta2, double eps, double weight_decay,
+                  double grad_scale) {
+  TORCH_CHECK(table.is_cuda() && table.dim() == 2 && table.is_contiguous() &&
+              table.scalar_type() == torch::kFloat32,
+              "sparse_apply: table must be contiguous fp32 [V,D] on GPU");
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == torch::kInt64 &&
+              ids.dim() == 1, "sparse_apply: ids must be i64 [n] on GPU");
+  TORCH_CHECK(opt >= SPARSE_SGD && opt <= SPARSE_ADAM,
+              "sparse_apply: unknown optimizer code ", opt);
+  const long n = ids.numel(), V = table.size(0);
+  const int D = table.size(1);
+  TORCH_CHECK(grads.is_cuda() && grads.numel() == n * D,
+              "sparse_apply: grads must be [n,D] on GPU");
+  const long total = table.numel();
+  float* s1 = opt_f32(state1, total, "state1");
+  float* s2 = opt_f32(state2, total, "state2");
+  bf16_t* shp = opt_bf16(shadow, total, "bf16_out");
+  TORCH_CHECK((s1 == nullptr || state1.is_contiguous()) &&
+              (s2 == nullptr || state2.is_contiguous()) &&
+              (shp == nullptr || shadow.is_contiguous()),
+              "sparse_apply: state/shadow must be contiguous");
+  TORCH_CHECK(opt == SPARSE_SGD || s1 != nullptr,
+              "sparse_apply: optimizer state tensor missing");
+  TORCH_CHECK(opt != SPARSE_ADAM || (s2 != nullptr && step >= 1),
+              "sparse_apply: adam needs exp_avg_sq and step >= 1");
+  if (n == 0 || D == 0) return;   // a zero-size grid is a launch error
+  bool gb;
+  const void* g = grad_ptr(grads, &gb);
+  auto st = torch::sort(ids, /*stable=*/true, /*dim=*/0,
+                        /*descending=*/false);
+  const torch::Tensor sorted = std::get<0>(st), perm = std::get<1>(st);
+  torch::Tensor scratch;
+  float* scratch_p = nullptr;
+  const long srows = sparse_scratch_rows(n);
+  if (srows > 0) {
+    scratch = torch::empty({srows, (long)D},
+                           table.options().dtype(torch::kFloat32));
+    scratch_p = scratch.data_ptr<float>();
+  }
+  SparseHp hp;
+  hp.lr = (float)lr;
+  hp.gscale = (float)grad_scale;
+  hp.wd = (float)weight_decay;
+  hp.beta1 = (float)beta1;
+  hp.beta2 = (float)beta2;
+  hp.eps = (float)eps;
+  // Adam constants in double, rounded once: fp32 (1.f - 0.999f) is off by
+  // 4.7e-5 relative, which a hot row's large summed gradient makes
+  // visible in exp_avg_sq
+  hp.omb1 = (float)(1.0 - beta1);
+  hp.omb2 = (float)(1.0 - beta2);
+  hp.bc1 = (float)(1.0 - std::pow(beta1, (double)step));
+  hp.bc2 = (float)(1.0 - std::pow(beta2, (double)step));
+  launch_sparse_apply((int)opt, table.data_ptr<float>(),
+                      sorted.data_ptr<long>(), perm.data_ptr<long>(), g, gb,
+                      scratch_p, s1, s2, shp, n, D, V, hp, cur_stream());
+}
+
 torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor act) {
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16 &&
               dy.is_contiguous() && act.is_contiguous() &&
@@ -1354,6 +1421,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_bwd_weight_out", &conv2d_bwd_weight_out);
   m.def("embedding_gather", &embedding_gather);
   m.def("embedding_scatter_add", &embedding_scatter_add);
+  m.def("sparse_apply", &sparse_apply,
+        "fused sparse SGD/momentum/Adagrad/Adam apply + bf16 shadow",
+        py::arg("table"), py::arg("ids"), py::arg("grads"),
+        py::arg("state1"), py::arg("state2"), py::arg("bf16_out"),
+        py::arg("opt"), py::arg("step"), py::arg("lr"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("grad_scale"));
   m.def("relu_bwd", &relu_bwd);
   m.def("colsum", &colsum, py::arg("x"), py::arg("out"));
 }

@@ -1,0 +1,27 @@
+// Host-side interface of sparse_apply.hip (shared with the binding TU).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "common.h"
+
+enum SparseOpt {
+  SPARSE_SGD = 0,
+  SPARSE_SGD_MOM = 1,   // state1 = momentum buffer, beta1 = momentum
+  SPARSE_ADAGRAD = 2,   // state1 = accumulator
+  SPARSE_ADAM = 3,      // state1 = exp_avg, state2 = exp_avg_sq
+};
+
+struct SparseHp {
+  float lr, gscale, wd;
+  float beta1, beta2, eps;
+  float omb1, omb2;     // 1-beta1, 1-beta2, rounded once from double
+  float bc1, bc2;       // Adam bias corrections (from step)
+};
+
+long sparse_scratch_rows(long n);
+void launch_sparse_apply(int opt, float* table, const long* sorted,
+                         const long* perm, const void* grads, bool g_bf16,
+                         float* scratch, float* s1, float* s2, bf16_t* shadow,
+                         long n, int D, long V, const SparseHp& hp,
+                         hipStream_t stream);

@@ -15,6 +15,11 @@ gradients back:
   scatter-adding ``-lr * grad`` into the fp32 master with the HIP
   scatter-add kernel (duplicate ids accumulate, matching TF's
   sparse-apply semantics) and refreshes the touched bf16 shadow rows.
+  Tables built with momentum, Adagrad or Adam (or ``fused_apply=True``)
+  instead sum each row's duplicates and run one optimizer step per
+  touched row in the fused HIP sparse-apply pass
+  (``csrc/sparse_apply.hip``): master, state and shadow in one kernel,
+  no float atomics, no host sync.
 
 Transport rides ``ps.chan.Chan`` pair channels: under RCCL every
 tensor (header, ids, rows, grads) is DEVICE-RESIDENT end to end — the
@@ -41,18 +46,59 @@ from tfmesos_amd.ps.chan import Chan, make_pair_chans  # noqa: F401
 
 
 class EmbeddingTable(object):
-    """One PS-resident table: fp32 master + bf16 pull shadow."""
+    """One PS-resident table: fp32 master + bf16 pull shadow (+ fp32
+    optimizer state rows).
 
-    def __init__(self, name, rows, dim, device="cpu", lr=0.01, seed=0):
+    optimizer: "sgd" (hparams momentum, weight_decay), "adagrad" (eps,
+    weight_decay) or "adam" (beta1, beta2, eps, weight_decay; lazy — only
+    touched rows and their moments move; ``step`` advances once per
+    push). Duplicate ids of one push are summed and the update runs once
+    per touched row (TF sparse-apply semantics).
+
+    Plain SGD keeps the scatter-add push unless ``fused_apply=True``
+    opts it into the fused sparse-apply kernel; every other
+    configuration always uses the fused kernel (``ops.sparse_*``)."""
+
+    _HPARAMS = {
+        "sgd": {"momentum": 0.0, "weight_decay": 0.0},
+        "adagrad": {"eps": 1e-10, "weight_decay": 0.0},
+        "adam": {"beta1": 0.9, "beta2": 0.999, "eps": 1e-8,
+                 "weight_decay": 0.0},
+    }
+    _STATE = {"sgd": (), "adagrad": ("accum",),
+              "adam": ("exp_avg", "exp_avg_sq")}
+
+    def __init__(self, name, rows, dim, device="cpu", lr=0.01, seed=0,
+                 optimizer="sgd", fused_apply=False, **hparams):
+        if optimizer not in self._HPARAMS:
+            raise ValueError("unknown sparse optimizer %r (have %s)"
+                             % (optimizer, sorted(self._HPARAMS)))
+        hp = dict(self._HPARAMS[optimizer])
+        for k, v in hparams.items():
+            if k not in hp:
+                raise ValueError("optimizer %r has no hyper-parameter %r"
+                                 % (optimizer, k))
+            hp[k] = v
         self.name = name
         self.rows = rows
         self.dim = dim
         self.lr = lr
+        self.optimizer = optimizer
+        self.hparams = hp
+        self.step = 0
         self.device = torch.device(device)
         g = torch.Generator().manual_seed(seed)
         init = torch.rand(rows, dim, generator=g) / dim ** 0.5
         self.master = init.to(self.device)
         self.shadow = self.master.to(torch.bfloat16)
+        names = self._STATE[optimizer]
+        if optimizer == "sgd" and hp["momentum"]:
+            names = ("momentum_buf",)
+        self.state = {k: torch.zeros(rows, dim, device=self.device)
+                      for k in names}
+        # the scatter-add path can only add -lr*g: anything else is fused
+        self.fused = bool(fused_apply or optimizer != "sgd"
+                          or hp["momentum"] or hp["weight_decay"])
         self.lock = threading.Lock()
 
     def pull(self, ids):
@@ -61,15 +107,67 @@ class EmbeddingTable(object):
             return ops.embedding_gather(self.shadow, ids)
 
     def push(self, ids, grads, lr=None):
-        """SGD sparse apply: master[ids] -= lr*grads (duplicates sum),
-        then refresh the touched shadow rows."""
+        """Sparse apply of one push (duplicates sum); the touched shadow
+        rows are refreshed."""
         lr = self.lr if lr is None else lr
         with self.lock:
+            if self.fused:
+                self._push_fused(ids, grads, lr)
+                return
             g = grads.to(self.master.dtype) * (-lr)
             ops.embedding_scatter_add(self.master, ids, g)
             uniq = torch.unique(ids)
             self.shadow.index_copy_(
                 0, uniq, self.master.index_select(0, uniq).to(torch.bfloat16))
+
+    def _push_fused(self, ids, grads, lr):
+        hp, st = self.hparams, self.state
+        self.step += 1
+        if self.optimizer == "sgd":
+            ops.sparse_sgd(self.master, ids, grads, lr,
+                           momentum=hp["momentum"],
+                           momentum_buf=st.get("momentum_buf"),
+                           weight_decay=hp["weight_decay"],
+                           bf16_out=self.shadow)
+        elif self.optimizer == "adagrad":
+            ops.sparse_adagrad(self.master, ids, grads, st["accum"], lr,
+                               eps=hp["eps"],
+                               weight_decay=hp["weight_decay"],
+                               bf16_out=self.shadow)
+        else:
+            ops.sparse_adam(self.master, ids, grads, st["exp_avg"],
+                            st["exp_avg_sq"], self.step, lr,
+                            beta1=hp["beta1"], beta2=hp["beta2"],
+                            eps=hp["eps"], weight_decay=hp["weight_decay"],
+                            bf16_out=self.shadow)
+
+    def state_dict(self):
+        """Master, optimizer state and step (CPU copies) — a table
+        resumed without its Adagrad/Adam state trains wrongly."""
+        with self.lock:
+            return {
+                "optimizer": self.optimizer,
+                "master": self.master.cpu().clone(),
+                "state": {k: v.cpu().clone() for k, v in self.state.items()},
+                "step": self.step,
+            }
+
+    def load_state_dict(self, sd):
+        """Copy INTO the existing buffers (callers may hold views) and
+        rebuild the bf16 shadow from the restored master."""
+        if sd["optimizer"] != self.optimizer:
+            raise ValueError("checkpoint is for optimizer %r, table uses %r"
+                             % (sd["optimizer"], self.optimizer))
+        if set(sd["state"]) != set(self.state):
+            raise ValueError("checkpoint state %s does not match table "
+                             "state %s" % (sorted(sd["state"]),
+                                           sorted(self.state)))
+        with self.lock:
+            self.master.copy_(sd["master"])
+            for k, v in sd["state"].items():
+                self.state[k].copy_(v)
+            self.step = int(sd["step"])
+            self.shadow.copy_(self.master.to(torch.bfloat16))
 
 
 def make_sparse_pair_groups(ps_ranks, worker_ranks):
