@@ -24,6 +24,7 @@ sources = [
     os.path.join(CSRC, "pool.hip"),
     os.path.join(CSRC, "softmax_xent.hip"),
     os.path.join(CSRC, "embedding.hip"),
+    os.path.join(CSRC, "embedding_bag.hip"),
     os.path.join(CSRC, "sparse_apply.hip"),
     os.path.join(CSRC, "elementwise.hip"),
 ]

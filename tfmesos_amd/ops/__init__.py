@@ -12,7 +12,10 @@ runtime: fused optimizer apply (SGD/momentum, Adagrad,
 Adam), bf16 GEMM with fused bias+ReLU epilogue, fused softmax
 cross-entropy, embedding gather / scatter-add, fused sparse optimizer
 apply for embedding rows (sparse_sgd / sparse_adagrad / sparse_adam —
-TF's SparseApply*: duplicates summed, one update per touched row).
+TF's SparseApply*: duplicates summed, one update per touched row), and
+pooled (bag) lookups: embedding_bag forward (TF's embedding_lookup_sparse,
+combiner sum / mean, optional weights) and the same sparse applies fed
+bag gradients (``offsets=``).
 """
 
 import torch
@@ -330,6 +333,79 @@ def embedding_scatter_add(table, ids, rows):
     table.index_add_(0, ids, rows.to(table.dtype))
 
 
+# ------------------------------------------------------ pooled (bag) lookup
+#
+# A bagged request is CSR-shaped: ids int64 [n], offsets int64 [B+1]
+# (nondecreasing, offsets[0] == 0, offsets[B] == n; bag b is positions
+# [offsets[b], offsets[b+1])), optional weights fp32 [n] (default 1).
+# W_b = sum of w_i over ALL positions of bag b; the coefficient of position
+# i is c_i = w_i (sum) or w_i / W_b (mean), 0 when W_b == 0. Ids outside
+# [0, V) contribute nothing but still count in W_b. offsets is a caller
+# contract: the CPU path validates it (ValueError); the GPU path does not
+# (no device->host sync) — its kernels clamp every position they derive
+# from it, so a violating input stays in bounds with an unspecified result.
+
+def _bag_check(ids, offsets, weights, combiner):
+    if combiner not in ("sum", "mean"):
+        raise ValueError("unknown combiner %r (have 'sum', 'mean')"
+                         % (combiner,))
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("offsets must be int64 [B+1]")
+    if weights is not None and tuple(weights.shape) != (ids.numel(),):
+        raise ValueError("weights must be [n] = [%d], got %s"
+                         % (ids.numel(), tuple(weights.shape)))
+
+
+def _bag_expand_cpu(ids, offsets, weights, combiner):
+    """CPU reference of the expansion: validates offsets, returns the
+    per-position bag row ``bag_of`` and coefficient ``c`` (fp32)."""
+    n, B = ids.numel(), offsets.numel() - 1
+    lens = offsets[1:] - offsets[:-1]
+    if int(offsets[0]) != 0 or int(offsets[-1]) != n or bool((lens < 0).any()):
+        raise ValueError("offsets must be nondecreasing with offsets[0] == 0 "
+                         "and offsets[-1] == n = %d" % n)
+    bag_of = torch.repeat_interleave(torch.arange(B), lens)
+    c = weights.float() if weights is not None else torch.ones(n)
+    if combiner == "mean":
+        W = torch.zeros(B).index_add_(0, bag_of, c)[bag_of]
+        c = torch.where(W == 0, torch.zeros(n), c / W)
+    return bag_of, c
+
+
+def _bag_weights(weights, dev):
+    if weights is None:
+        return torch.empty(0, device=dev)
+    return weights.to(torch.float32).contiguous()
+
+
+@torch.no_grad()
+def embedding_bag(table, ids, offsets, weights=None, combiner="sum",
+                  out_dtype=None):
+    """out[b] = sum_i c_i * table[ids[i]] over bag b: fp32 accumulation in
+    position order, rounded once to out_dtype; an empty bag gives a zero
+    row. table [V,D] bf16 or fp32; out_dtype defaults to the table's,
+    torch.float32 is allowed for a bf16 table (long bags lose bits in
+    bf16). GPU: csrc/embedding_bag.hip, no atomics, no host sync."""
+    _bag_check(ids, offsets, weights, combiner)
+    if table.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("embedding_bag: table must be bf16 or fp32")
+    out_dtype = table.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (table.dtype, torch.float32):
+        raise ValueError("embedding_bag: out_dtype must be the table's dtype "
+                         "or torch.float32")
+    if table.is_cuda:
+        return _ext().embedding_bag(
+            table, ids.contiguous(), offsets.contiguous(),
+            _bag_weights(weights, table.device), combiner == "mean",
+            out_dtype == torch.float32)
+    bag_of, c = _bag_expand_cpu(ids, offsets, weights, combiner)
+    keep = (ids >= 0) & (ids < table.shape[0])
+    rows = table.index_select(0, ids[keep]).float()
+    out = torch.zeros(offsets.numel() - 1, table.shape[1])
+    out.index_add_(0, bag_of[keep], c[keep, None] * rows)
+    return out.to(out_dtype)
+
+
 # ------------------------------------------------- sparse optimizer applies
 #
 # TF SparseApply* semantics: per touched row r the summed gradient is
@@ -338,14 +414,31 @@ def embedding_scatter_add(table, ids, rows):
 # are ignored; untouched rows (and their state) never move. GPU: one fused
 # HIP pass over master + state + bf16 shadow (csrc/sparse_apply.hip), no
 # float atomics, bit-reproducible, no host sync.
+#
+# Pooled push (``offsets=`` given): ids/offsets/weights/combiner describe
+# bags as for embedding_bag, grads is [B,D] BAG gradients and position i of
+# bag b contributes c_i * grads[b]; everything above then holds unchanged.
+# The GPU kernel reads the bag rows through the indirection (the n x D
+# expanded rows are never built); the CPU reference builds them.
 
 _SPARSE_SGD, _SPARSE_SGD_MOM, _SPARSE_ADAGRAD, _SPARSE_ADAM = 0, 1, 2, 3
 
 
 def _sparse_hip(code, param, ids, grads, s1, s2, bf16_out, step, lr, beta1,
-                beta2, eps, weight_decay, grad_scale):
+                beta2, eps, weight_decay, grad_scale, bag=None):
     dev = param.device
     ef = torch.empty(0, device=dev)
+    if bag is not None:
+        offsets, weights, combiner = bag
+        _ext().sparse_apply_bag(
+            param, ids.contiguous(), offsets.contiguous(),
+            _bag_weights(weights, dev), grads,
+            s1 if s1 is not None else ef, s2 if s2 is not None else ef,
+            bf16_out if bf16_out is not None
+            else torch.empty(0, dtype=torch.bfloat16, device=dev),
+            code, int(step), combiner == "mean", float(lr), float(beta1),
+            float(beta2), float(eps), float(weight_decay), float(grad_scale))
+        return
     _ext().sparse_apply(
         param, ids, grads, s1 if s1 is not None else ef,
         s2 if s2 is not None else ef,
@@ -353,6 +446,25 @@ def _sparse_hip(code, param, ids, grads, s1, s2, bf16_out, step, lr, beta1,
         else torch.empty(0, dtype=torch.bfloat16, device=dev),
         code, int(step), float(lr), float(beta1), float(beta2), float(eps),
         float(weight_decay), float(grad_scale))
+
+
+def _bag_of_call(ids, grads, offsets, weights, combiner):
+    """(offsets, weights, combiner) of a pooled call, None for a row call."""
+    if offsets is None:
+        if weights is not None:
+            raise ValueError("weights need offsets (a pooled push)")
+        return None
+    _bag_check(ids, offsets, weights, combiner)
+    if grads.dim() != 2 or grads.shape[0] != offsets.numel() - 1:
+        raise ValueError("pooled push: grads must be [B,D] = [%d,D], got %s"
+                         % (offsets.numel() - 1, tuple(grads.shape)))
+    return offsets, weights, combiner
+
+
+def _bag_rows_cpu(ids, grads, bag):
+    """CPU reference: the per-position rows c_i * grads[bag_of[i]], fp32."""
+    bag_of, c = _bag_expand_cpu(ids, *bag)
+    return c[:, None] * grads.float()[bag_of]
 
 
 def _sparse_cpu(param, ids, grads, states, bf16_out, dense_step):
@@ -378,19 +490,24 @@ def _sparse_cpu(param, ids, grads, states, bf16_out, dense_step):
 
 @torch.no_grad()
 def sparse_sgd(param, ids, grads, lr, momentum=0.0, momentum_buf=None,
-               weight_decay=0.0, bf16_out=None, grad_scale=1.0):
+               weight_decay=0.0, bf16_out=None, grad_scale=1.0, *,
+               offsets=None, weights=None, combiner="sum"):
     """Sparse SGD(+momentum, +wd) on the rows ``ids`` of an fp32 [V,D]
     master; grads [n,D] bf16 or fp32. bf16_out ([V,D] shadow) gets the
-    touched rows refreshed in the same pass."""
+    touched rows refreshed in the same pass. With ``offsets``: a pooled
+    push, grads [B,D] bag gradients."""
     if momentum and momentum_buf is None:
         raise ValueError("sparse_sgd: momentum needs a momentum_buf")
     if not momentum:
         momentum_buf = None
+    bag = _bag_of_call(ids, grads, offsets, weights, combiner)
     if param.is_cuda:
         _sparse_hip(_SPARSE_SGD_MOM if momentum else _SPARSE_SGD, param, ids,
                     grads, momentum_buf, None, bf16_out, 1, lr, momentum, 0.0,
-                    0.0, weight_decay, grad_scale)
+                    0.0, weight_decay, grad_scale, bag=bag)
         return
+    if bag is not None:
+        grads = _bag_rows_cpu(ids, grads, bag)
 
     def step(p, g, *mb):
         fused_sgd(p, g, lr, momentum=momentum, weight_decay=weight_decay,
@@ -401,13 +518,19 @@ def sparse_sgd(param, ids, grads, lr, momentum=0.0, momentum_buf=None,
 
 @torch.no_grad()
 def sparse_adagrad(param, ids, grads, accum, lr, eps=1e-10,
-                   weight_decay=0.0, bf16_out=None, grad_scale=1.0):
+                   weight_decay=0.0, bf16_out=None, grad_scale=1.0, *,
+                   offsets=None, weights=None, combiner="sum"):
     """Sparse Adagrad: a += G^2; p -= lr*G/(sqrt(a)+eps) per touched row
-    (ids [3,3] with grads g,-g leave row and accumulator untouched)."""
+    (ids [3,3] with grads g,-g leave row and accumulator untouched).
+    With ``offsets``: a pooled push, grads [B,D] bag gradients."""
+    bag = _bag_of_call(ids, grads, offsets, weights, combiner)
     if param.is_cuda:
         _sparse_hip(_SPARSE_ADAGRAD, param, ids, grads, accum, None,
-                    bf16_out, 1, lr, 0.0, 0.0, eps, weight_decay, grad_scale)
+                    bf16_out, 1, lr, 0.0, 0.0, eps, weight_decay, grad_scale,
+                    bag=bag)
         return
+    if bag is not None:
+        grads = _bag_rows_cpu(ids, grads, bag)
 
     def step(p, g, a):
         fused_adagrad(p, g, a, lr, eps=eps, weight_decay=weight_decay,
@@ -418,14 +541,19 @@ def sparse_adagrad(param, ids, grads, accum, lr, eps=1e-10,
 @torch.no_grad()
 def sparse_adam(param, ids, grads, exp_avg, exp_avg_sq, step, lr,
                 beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
-                bf16_out=None, grad_scale=1.0):
+                bf16_out=None, grad_scale=1.0, *, offsets=None, weights=None,
+                combiner="sum"):
     """Lazy sparse Adam: only touched rows (and their m, v) move; the
-    bias corrections come from ``step`` (>= 1)."""
+    bias corrections come from ``step`` (>= 1). With ``offsets``: a
+    pooled push, grads [B,D] bag gradients."""
+    bag = _bag_of_call(ids, grads, offsets, weights, combiner)
     if param.is_cuda:
         _sparse_hip(_SPARSE_ADAM, param, ids, grads, exp_avg, exp_avg_sq,
                     bf16_out, step, lr, beta1, beta2, eps, weight_decay,
-                    grad_scale)
+                    grad_scale, bag=bag)
         return
+    if bag is not None:
+        grads = _bag_rows_cpu(ids, grads, bag)
 
     def dense(p, g, m, v):
         fused_adam(p, g, m, v, step, lr, beta1=beta1, beta2=beta2, eps=eps,

@@ -1,0 +1,187 @@
+// Pooled (bag) embedding pull: out[b] = sum_i c_i * table[ids[i]] over the
+// positions i of CSR bag b (TF's embedding_lookup_sparse, combiner sum or
+// mean, optional per-id weights; coefficient rule in bag.h).
+//
+//   * one wave owns one (bag, 256-column tile): it reads the bag's ids
+//     (and weights) 64 positions at a time, one per lane, broadcasts each
+//     with a wave shuffle, keeps 4 row loads in flight and accumulates in
+//     fp32 registers in position order; the row is rounded once on store.
+//     Fixed order, no atomics => bit-reproducible.
+//   * D % 4 == 0 and 16-byte aligned bases: lane l owns columns 4l..4l+3
+//     of the tile (bf16x4 / f32x4 accesses). Otherwise a scalar path:
+//     lane l owns columns l, l+64, l+128, l+192 (a vector access on an
+//     odd-D row would be misaligned).
+//   * ids outside [0, V) contribute nothing (their rows are never read)
+//     but still count in W_b.
+//   * the grid is sized from B and D only; nothing is read back.
+//   * a single very long bag stays with one wave per tile (no chunk rule
+//     on the forward side).
+#include "common.h"
+
+#include "bag.h"
+
+namespace {
+
+constexpr int WAVES = 4;    // waves per block
+constexpr int TILE = 256;   // columns per wave
+constexpr int ACC = 4;      // accumulators per lane = TILE / WAVE
+
+// The lane's ACC elements of one table row's tile, as fp32.
+template <typename T, int VEC>
+DEVINL void ld_tile(const T* __restrict__ row, int c0, int lane, int D,
+                    float (&v)[ACC]) {
+  if constexpr (VEC == 4) {
+    const int col = c0 + lane * 4;
+    if (col < D) {
+      if constexpr (sizeof(T) == 2) {
+        const bf16x4 t = *(const bf16x4*)(const __bf16*)(row + col);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (float)t[e];
+      } else {
+        const f32x4 t = *(const f32x4*)(row + col);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = t[e];
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = 0.f;
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < ACC; ++e) {
+      const int col = c0 + e * WAVE + lane;
+      float x = 0.f;
+      if (col < D) {
+        if constexpr (sizeof(T) == 2) x = bf2f(*(const bf16_t*)(row + col));
+        else x = *(const float*)(row + col);
+      }
+      v[e] = x;
+    }
+  }
+}
+
+template <typename O, int VEC>
+DEVINL void st_tile(O* __restrict__ row, int c0, int lane, int D,
+                    const float (&v)[ACC]) {
+  if constexpr (VEC == 4) {
+    const int col = c0 + lane * 4;
+    if (col >= D) return;
+    if constexpr (sizeof(O) == 2) {
+      bf16x4 t;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) t[e] = (__bf16)v[e];
+      *(bf16x4*)(__bf16*)(row + col) = t;
+    } else {
+      f32x4 t;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) t[e] = v[e];
+      *(f32x4*)(row + col) = t;
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < ACC; ++e) {
+      const int col = c0 + e * WAVE + lane;
+      if (col < D) {
+        if constexpr (sizeof(O) == 2) *(bf16_t*)(row + col) = f2bf(v[e]);
+        else *(float*)(row + col) = v[e];
+      }
+    }
+  }
+}
+
+template <typename T, typename O, int VEC>
+__global__ __launch_bounds__(WAVES * WAVE) void embedding_bag_kernel(
+    const T* __restrict__ table, const long* __restrict__ ids,
+    const long* __restrict__ offsets, const float* __restrict__ weights,
+    O* __restrict__ out, long B, long n, int D, long V, int tiles,
+    int mean) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const long w = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (w >= B * tiles) return;   // wave-uniform
+  const long b = w / tiles;
+  const int c0 = (int)(w % tiles) * TILE;
+  long s, e;
+  bag_range(offsets, b, n, s, e);
+  const float W = mean ? bag_weight_sum(weights, s, e, lane) : 0.f;
+  float acc[ACC];
+#pragma unroll
+  for (int k = 0; k < ACC; ++k) acc[k] = 0.f;
+  for (long p0 = s; p0 < e; p0 += WAVE) {
+    const long p = p0 + lane;
+    long id = p < e ? ids[p] : -1;
+    const bool valid = id >= 0 && id < V;
+    float cf = 0.f;
+    if (valid) cf = bag_coef(weights ? weights[p] : 1.f, W, mean != 0);
+    else id = 0;
+    // walk the valid lanes in position order, 4 row loads in flight
+    unsigned long long m = __ballot(valid);
+    while (__popcll(m) >= 4) {
+      const int k0 = __ffsll(m) - 1; m &= m - 1;
+      const int k1 = __ffsll(m) - 1; m &= m - 1;
+      const int k2 = __ffsll(m) - 1; m &= m - 1;
+      const int k3 = __ffsll(m) - 1; m &= m - 1;
+      const long r0 = __shfl(id, k0), r1 = __shfl(id, k1);
+      const long r2 = __shfl(id, k2), r3 = __shfl(id, k3);
+      const float f0 = __shfl(cf, k0), f1 = __shfl(cf, k1);
+      const float f2 = __shfl(cf, k2), f3 = __shfl(cf, k3);
+      float v0[ACC], v1[ACC], v2[ACC], v3[ACC];
+      ld_tile<T, VEC>(table + r0 * D, c0, lane, D, v0);
+      ld_tile<T, VEC>(table + r1 * D, c0, lane, D, v1);
+      ld_tile<T, VEC>(table + r2 * D, c0, lane, D, v2);
+      ld_tile<T, VEC>(table + r3 * D, c0, lane, D, v3);
+#pragma unroll
+      for (int k = 0; k < ACC; ++k)
+        acc[k] = (((acc[k] + f0 * v0[k]) + f1 * v1[k]) + f2 * v2[k]) +
+                 f3 * v3[k];
+    }
+    while (m) {
+      const int k0 = __ffsll(m) - 1; m &= m - 1;
+      const long r = __shfl(id, k0);
+      const float f = __shfl(cf, k0);
+      float v[ACC];
+      ld_tile<T, VEC>(table + r * D, c0, lane, D, v);
+#pragma unroll
+      for (int k = 0; k < ACC; ++k) acc[k] += f * v[k];
+    }
+  }
+  st_tile<O, VEC>(out + b * D, c0, lane, D, acc);   // empty bag: zeros
+}
+
+template <typename T, typename O>
+void launch_typed(const T* table, const long* ids, const long* offsets,
+                  const float* weights, O* out, long B, long n, int D, long V,
+                  bool mean, hipStream_t stream) {
+  const int tiles = (D + TILE - 1) / TILE;
+  const long waves = B * tiles;
+  const dim3 block(WAVES * WAVE);
+  const dim3 grid((unsigned)((waves + WAVES - 1) / WAVES));
+  // vector path needs 16-byte aligned rows: D % 4 == 0 and aligned bases
+  const uintptr_t bases = (uintptr_t)table | (uintptr_t)out;
+  if ((D % 4) == 0 && (bases % 16) == 0)
+    hipLaunchKernelGGL((embedding_bag_kernel<T, O, 4>), grid, block, 0,
+                       stream, table, ids, offsets, weights, out, B, n, D, V,
+                       tiles, (int)mean);
+  else
+    hipLaunchKernelGGL((embedding_bag_kernel<T, O, 1>), grid, block, 0,
+                       stream, table, ids, offsets, weights, out, B, n, D, V,
+                       tiles, (int)mean);
+}
+
+}  // namespace
+
+// table [V,D] bf16 or fp32; out [B,D] in the table's dtype, or fp32 from
+// a bf16 table. weights may be null (all 1). B, n, D > 0.
+void launch_embedding_bag(const void* table, bool t_bf16, const long* ids,
+                          const long* offsets, const float* weights,
+                          void* out, bool o_bf16, long B, long n, int D,
+                          long V, bool mean, hipStream_t stream) {
+  if (t_bf16 && o_bf16)
+    launch_typed((const bf16_t*)table, ids, offsets, weights, (bf16_t*)out, B,
+                 n, D, V, mean, stream);
+  else if (t_bf16)
+    launch_typed((const bf16_t*)table, ids, offsets, weights, (float*)out, B,
+                 n, D, V, mean, stream);
+  else
+    launch_typed((const float*)table, ids, offsets, weights, (float*)out, B,
+                 n, D, V, mean, stream);
+}

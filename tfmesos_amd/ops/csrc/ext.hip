@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <climits>
+
 #include "common.h"
 #include "sparse_apply.h"
 
@@ -53,6 +55,9 @@ void launch_scatter_add_bf16(float*, const long*, const bf16_t*, long, int,
                              long, hipStream_t);
 void launch_scatter_add_f32(float*, const long*, const float*, long, int,
                             long, hipStream_t);
+void launch_embedding_bag(const void*, bool, const long*, const long*,
+                          const float*, void*, bool, long, long, int, long,
+                          bool, hipStream_t);
 void launch_relu_bwd(const bf16_t*, const bf16_t*, bf16_t*, long,
                      hipStream_t);
 void launch_add_n(const bf16_t* const*, int, bf16_t*, long, hipStream_t);
@@ -747,6 +752,77 @@ void embedding_scatter_add(torch::Tensor table, torch::Tensor ids,
                            rows.data_ptr<float>(), n, D, V, cur_stream());
 }
 
+// Hyper-parameters of one sparse apply (row or bag mode).
+SparseHp sparse_hp(long step, double lr, double beta1, double beta2,
+                   double eps, double weight_decay, double grad_scale) {
+  SparseHp hp;
+  hp.lr = (float)lr;
+  hp.gscale = (float)grad_scale;
+  hp.wd = (float)weight_decay;
+  hp.beta1 = (float)beta1;
+  hp.beta2 = (float)beta2;
+  hp.eps = (float)eps;
+  // Adam constants in double, rounded once: fp32 (1.f - 0.999f) is off by
+  // 4.7e-5 relative, which a hot row's large summed gradient makes
+  // visible in exp_avg_sq
+  hp.omb1 = (float)(1.0 - beta1);
+  hp.omb2 = (float)(1.0 - beta2);
+  hp.bc1 = (float)(1.0 - std::pow(beta1, (double)step));
+  hp.bc2 = (float)(1.0 - std::pow(beta2, (double)step));
+  return hp;
+}
+
+// CSR bag arguments shared by embedding_bag and sparse_apply_bag: ids i64
+// [n], offsets i64 [B+1], weights fp32 [n] or empty. The contents of
+// offsets are a caller contract (not read back: no device->host sync; the
+// kernels clamp what they derive from it). Returns the weights pointer.
+const float* bag_args(const char* op, const torch::Tensor& ids,
+                      const torch::Tensor& offsets,
+                      const torch::Tensor& weights) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == torch::kInt64 &&
+              ids.dim() == 1 && ids.is_contiguous(),
+              op, ": ids must be contiguous i64 [n] on GPU");
+  TORCH_CHECK(offsets.is_cuda() && offsets.scalar_type() == torch::kInt64 &&
+              offsets.dim() == 1 && offsets.numel() >= 1 &&
+              offsets.is_contiguous(),
+              op, ": offsets must be contiguous i64 [B+1] on GPU");
+  TORCH_CHECK(offsets.numel() - 1 <= (long)INT_MAX,
+              op, ": too many bags");
+  if (weights.numel() == 0) return nullptr;   // unweighted (or n == 0)
+  TORCH_CHECK(weights.is_cuda() && weights.scalar_type() == torch::kFloat32 &&
+              weights.is_contiguous() && weights.numel() == ids.numel(),
+              op, ": weights must be contiguous fp32 [n] on GPU");
+  return weights.data_ptr<float>();
+}
+
+// Pooled pull (embedding_bag.hip): out[b] = sum_i c_i * table[ids[i]] over
+// bag b, fp32 accumulation in position order, rounded once. out is the
+// table's dtype, or fp32 from a bf16 table with out_f32.
+torch::Tensor embedding_bag(torch::Tensor table, torch::Tensor ids,
+                            torch::Tensor offsets, torch::Tensor weights,
+                            bool mean, bool out_f32) {
+  TORCH_CHECK(table.is_cuda() && table.dim() == 2 && table.is_contiguous(),
+              "embedding_bag: table must be contiguous [V,D] on GPU");
+  const bool t_bf16 = table.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(t_bf16 || table.scalar_type() == torch::kFloat32,
+              "embedding_bag: table must be bf16 or fp32");
+  const float* w = bag_args("embedding_bag", ids, offsets, weights);
+  const long n = ids.numel(), V = table.size(0), B = offsets.numel() - 1;
+  const int D = table.size(1);
+  const bool o_bf16 = t_bf16 && !out_f32;
+  auto out = torch::empty({B, (long)D},
+                          table.options().dtype(o_bf16 ? torch::kBFloat16
+                                                       : torch::kFloat32));
+  if (B == 0 || D == 0) return out;   // a zero-size grid is a launch error
+  if (n == 0) return out.zero_();
+  TORCH_CHECK(B * ((D + 255) / 256) / 4 < (long)INT_MAX,
+              "embedding_bag: B x D too large for one grid");
+  launch_embedding_bag(table.data_ptr(), t_bf16, ids.data_ptr<long>(),
+                       offsets.data_ptr<long>(), w, out.data_ptr(), o_bf16, B,
+                       n, D, V, mean, cur_stream());
+  return out;
+}
+
 // Fused sparse optimizer apply (sparse_apply.hip): duplicates summed,
 // then ONE optimizer step per touched row, master + state + bf16 shadow
 // in the same pass. The stable sort of the ids is the inverted index
@@ -794,23 +870,71 @@ void sparse_apply(torch::Tensor table, torch::Tensor ids, torch::Tensor grads,
                            table.options().dtype(torch::kFloat32));
     scratch_p = scratch.data_ptr<float>();
   }
-  SparseHp hp;
-  hp.lr = (float)lr;
-  hp.gscale = (float)grad_scale;
-  hp.wd = (float)weight_decay;
-  hp.beta1 = (float)beta1;
-  hp.beta2 = (float)beta2;
-  hp.eps = (float)eps;
-  // Adam constants in double, rounded once: fp32 (1.f - 0.999f) is off by
-  // 4.7e-5 relative, which a hot row's large summed gradient makes
-  // visible in exp_avg_sq
-  hp.omb1 = (float)(1.0 - beta1);
-  hp.omb2 = (float)(1.0 - beta2);
-  hp.bc1 = (float)(1.0 - std::pow(beta1, (double)step));
-  hp.bc2 = (float)(1.0 - std::pow(beta2, (double)step));
+  const SparseHp hp = sparse_hp(step, lr, beta1, beta2, eps, weight_decay,
+                                grad_scale);
   launch_sparse_apply((int)opt, table.data_ptr<float>(),
                       sorted.data_ptr<long>(), perm.data_ptr<long>(), g, gb,
                       scratch_p, s1, s2, shp, n, D, V, hp, cur_stream());
+}
+
+// Pooled push: sparse_apply with grads = [B,D] bag gradients; position i
+// of bag b contributes c_i * grads[b] (coefficient rule in bag.h). One
+// expansion kernel derives bag row and coefficient per position from the
+// offsets; the sort of the ids stays the only plumbing; no host sync.
+void sparse_apply_bag(torch::Tensor table, torch::Tensor ids,
+                      torch::Tensor offsets, torch::Tensor weights,
+                      torch::Tensor grads, torch::Tensor state1,
+                      torch::Tensor state2, torch::Tensor shadow, long opt,
+                      long step, bool mean, double lr, double beta1,
+                      double beta2, double eps, double weight_decay,
+                      double grad_scale) {
+  TORCH_CHECK(table.is_cuda() && table.dim() == 2 && table.is_contiguous() &&
+              table.scalar_type() == torch::kFloat32,
+              "sparse_apply_bag: table must be contiguous fp32 [V,D] on GPU");
+  TORCH_CHECK(opt >= SPARSE_SGD && opt <= SPARSE_ADAM,
+              "sparse_apply_bag: unknown optimizer code ", opt);
+  const float* w = bag_args("sparse_apply_bag", ids, offsets, weights);
+  const long n = ids.numel(), V = table.size(0), B = offsets.numel() - 1;
+  const int D = table.size(1);
+  TORCH_CHECK(grads.is_cuda() && grads.numel() == B * D,
+              "sparse_apply_bag: grads must be [B,D] on GPU");
+  const long total = table.numel();
+  float* s1 = opt_f32(state1, total, "state1");
+  float* s2 = opt_f32(state2, total, "state2");
+  bf16_t* shp = opt_bf16(shadow, total, "bf16_out");
+  TORCH_CHECK((s1 == nullptr || state1.is_contiguous()) &&
+              (s2 == nullptr || state2.is_contiguous()) &&
+              (shp == nullptr || shadow.is_contiguous()),
+              "sparse_apply_bag: state/shadow must be contiguous");
+  TORCH_CHECK(opt == SPARSE_SGD || s1 != nullptr,
+              "sparse_apply_bag: optimizer state tensor missing");
+  TORCH_CHECK(opt != SPARSE_ADAM || (s2 != nullptr && step >= 1),
+              "sparse_apply_bag: adam needs exp_avg_sq and step >= 1");
+  if (n == 0 || B == 0 || D == 0) return;   // zero-size grid: launch error
+  bool gb;
+  const void* g = grad_ptr(grads, &gb);
+  auto iopt = ids.options();
+  auto bag_of = torch::zeros({n}, iopt.dtype(torch::kInt32));
+  auto coef = torch::zeros({n}, iopt.dtype(torch::kFloat32));
+  launch_bag_expand(offsets.data_ptr<long>(), w, bag_of.data_ptr<int>(),
+                    coef.data_ptr<float>(), B, n, mean, cur_stream());
+  auto st = torch::sort(ids, /*stable=*/true, /*dim=*/0,
+                        /*descending=*/false);
+  const torch::Tensor sorted = std::get<0>(st), perm = std::get<1>(st);
+  torch::Tensor scratch;
+  float* scratch_p = nullptr;
+  const long srows = sparse_scratch_rows(n);
+  if (srows > 0) {
+    scratch = torch::empty({srows, (long)D},
+                           table.options().dtype(torch::kFloat32));
+    scratch_p = scratch.data_ptr<float>();
+  }
+  const SparseHp hp = sparse_hp(step, lr, beta1, beta2, eps, weight_decay,
+                                grad_scale);
+  launch_sparse_apply_bag((int)opt, table.data_ptr<float>(),
+                          sorted.data_ptr<long>(), perm.data_ptr<long>(), g,
+                          gb, bag_of.data_ptr<int>(), coef.data_ptr<float>(),
+                          scratch_p, s1, s2, shp, n, D, V, hp, cur_stream());
 }
 
 torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor act) {
@@ -1426,6 +1550,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("table"), py::arg("ids"), py::arg("grads"),
         py::arg("state1"), py::arg("state2"), py::arg("bf16_out"),
         py::arg("opt"), py::arg("step"), py::arg("lr"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("grad_scale"));
+  m.def("embedding_bag", &embedding_bag,
+        "pooled (bag) embedding pull: sum / mean, optional weights",
+        py::arg("table"), py::arg("ids"), py::arg("offsets"),
+        py::arg("weights"), py::arg("mean"), py::arg("out_f32"));
+  m.def("sparse_apply_bag", &sparse_apply_bag,
+        "sparse_apply fed [B,D] bag gradients (pooled push)",
+        py::arg("table"), py::arg("ids"), py::arg("offsets"),
+        py::arg("weights"), py::arg("grads"), py::arg("state1"),
+        py::arg("state2"), py::arg("bf16_out"), py::arg("opt"),
+        py::arg("step"), py::arg("mean"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
         py::arg("grad_scale"));
   m.def("relu_bwd", &relu_bwd);

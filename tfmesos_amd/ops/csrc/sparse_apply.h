@@ -25,3 +25,16 @@ void launch_sparse_apply(int opt, float* table, const long* sorted,
                          float* scratch, float* s1, float* s2, bf16_t* shadow,
                          long n, int D, long V, const SparseHp& hp,
                          hipStream_t stream);
+
+// Pooled (bag) push: grads is [B,D], one row per CSR bag; position i of
+// the push contributes coef[i] * grads[bag_of[i]]. launch_bag_expand fills
+// bag_of / coef (int / fp32 [n], zeroed by the caller) from the offsets.
+void launch_bag_expand(const long* offsets, const float* weights, int* bag_of,
+                       float* coef, long B, long n, bool mean,
+                       hipStream_t stream);
+void launch_sparse_apply_bag(int opt, float* table, const long* sorted,
+                             const long* perm, const void* grads, bool g_bf16,
+                             const int* bag_of, const float* coef,
+                             float* scratch, float* s1, float* s2,
+                             bf16_t* shadow, long n, int D, long V,
+                             const SparseHp& hp, hipStream_t stream);

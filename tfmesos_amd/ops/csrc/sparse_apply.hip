@@ -30,8 +30,15 @@
 //     access on an odd-D row would be misaligned).
 //   * ids outside [0, V) are ignored (they sort to the ends and are
 //     never heads).
+//   * bag mode (pooled push): grads holds one row per CSR bag; position i
+//     contributes coef[i] * grads[bag_of[i]]. bag_expand_kernel derives
+//     bag_of / coef from the offsets (+ weights, combiner); the run
+//     summation takes them as a trailing BagIdx argument. An EMPTY
+//     trailing pack is row mode: the row-mode kernels keep their
+//     signature and compile to the code they had before bag mode.
 #include "common.h"
 
+#include "bag.h"
 #include "sparse_apply.h"
 
 namespace {
@@ -88,45 +95,84 @@ DEVINL void ld_grad(const G* __restrict__ p, float (&o)[VEC]) {
   }
 }
 
+// Bag mode's per-position indirection: position i of the push reads bag
+// gradient row bag_of[i], scaled by coef[i].
+struct BagIdx {
+  const int* __restrict__ bag_of;
+  const float* __restrict__ coef;
+};
+
+DEVINL const BagIdx& bag_idx(const BagIdx& b) { return b; }
+
 // acc += sum of grads[perm[j]] over the leading positions j in
 // [pos, pos+cap) whose sorted id equals id, in position order. The wave
 // reads the index 64 positions at a time (one per lane) and broadcasts
 // each source row; 4 row loads are kept in flight. All 64 lanes must
 // call this (ballot/shuffle); `active` lanes own columns.
-template <typename G, int VEC>
+// Bag mode (one trailing BagIdx): the term of position i = perm[j] is
+// coef[i] * grads[bag_of[i]] instead.
+template <typename G, int VEC, typename... BagP>
 DEVINL void sum_run(const long* __restrict__ sorted,
                     const long* __restrict__ perm,
                     const G* __restrict__ grads, long n, long pos, int cap,
                     long id, int D, int col, bool active, int lane,
-                    float (&acc)[VEC]) {
+                    float (&acc)[VEC], BagP... bagp) {
+  constexpr bool BAG = sizeof...(BagP) != 0;
   for (int done = 0; done < cap; done += WAVE) {
     const long j = pos + done + lane;
     const bool match = (done + lane < cap) && j < n && sorted[j] == id;
-    const long src = match ? perm[j] : 0;
+    long src = match ? perm[j] : 0;
+    float cf = 0.f;
+    if constexpr (BAG) {
+      const BagIdx& bi = bag_idx(bagp...);
+      if (match) {
+        cf = bi.coef[src];
+        src = bi.bag_of[src];
+      }
+    }
     const unsigned long long miss = ~__ballot(match);
     const int cnt = miss ? __ffsll(miss) - 1 : WAVE;
     int k = 0;
     for (; k + 4 <= cnt; k += 4) {
       const long r0 = __shfl(src, k), r1 = __shfl(src, k + 1);
       const long r2 = __shfl(src, k + 2), r3 = __shfl(src, k + 3);
+      float f0 = 1.f, f1 = 1.f, f2 = 1.f, f3 = 1.f;
+      if constexpr (BAG) {   // shuffles stay outside the divergent branch
+        f0 = __shfl(cf, k), f1 = __shfl(cf, k + 1);
+        f2 = __shfl(cf, k + 2), f3 = __shfl(cf, k + 3);
+      }
       if (active) {
         float v0[VEC], v1[VEC], v2[VEC], v3[VEC];
         ld_grad<G, VEC>(grads + r0 * D + col, v0);
         ld_grad<G, VEC>(grads + r1 * D + col, v1);
         ld_grad<G, VEC>(grads + r2 * D + col, v2);
         ld_grad<G, VEC>(grads + r3 * D + col, v3);
+        if constexpr (BAG) {
 #pragma unroll
-        for (int e = 0; e < VEC; ++e)
-          acc[e] = (((acc[e] + v0[e]) + v1[e]) + v2[e]) + v3[e];
+          for (int e = 0; e < VEC; ++e)
+            acc[e] = (((acc[e] + f0 * v0[e]) + f1 * v1[e]) + f2 * v2[e]) +
+                     f3 * v3[e];
+        } else {
+#pragma unroll
+          for (int e = 0; e < VEC; ++e)
+            acc[e] = (((acc[e] + v0[e]) + v1[e]) + v2[e]) + v3[e];
+        }
       }
     }
     for (; k < cnt; ++k) {
       const long r = __shfl(src, k);
+      float f = 1.f;
+      if constexpr (BAG) f = __shfl(cf, k);
       if (active) {
         float v[VEC];
         ld_grad<G, VEC>(grads + r * D + col, v);
+        if constexpr (BAG) {
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) acc[e] += v[e];
+          for (int e = 0; e < VEC; ++e) acc[e] += f * v[e];
+        } else {
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) acc[e] += v[e];
+        }
       }
     }
     if (cnt < WAVE) break;
@@ -163,11 +209,11 @@ DEVINL void apply_elem(float& pv, float& a, float& c, float g,
 
 // Pass 1 (only launched when n > CHUNK): the chunk heads of LONG runs
 // sum their <= CHUNK contributions into scratch[slot].
-template <typename G, int VEC>
+template <typename G, int VEC, typename... BagP>
 __global__ __launch_bounds__(WAVES * WAVE) void sparse_partial_kernel(
     const long* __restrict__ sorted, const long* __restrict__ perm,
     const G* __restrict__ grads, float* __restrict__ scratch, long n, int D,
-    long V) {
+    long V, BagP... bagp) {
   const int lane = threadIdx.x & (WAVE - 1);
   const long base = ((long)blockIdx.x * WAVES + (threadIdx.x >> 6)) * WAVE;
   const long i = base + lane;
@@ -203,20 +249,20 @@ __global__ __launch_bounds__(WAVES * WAVE) void sparse_partial_kernel(
 #pragma unroll
       for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
       sum_run<G, VEC>(sorted, perm, grads, n, pos, CHUNK, id, D, col, active,
-                      lane, acc);
+                      lane, acc, bagp...);
       if (active) st_f32<VEC>(scratch + slot * D + col, acc);
     }
   }
 }
 
 // Pass 2: one wave per touched row (run head) — sum, apply, store.
-template <typename G, int VEC, int OPT>
+template <typename G, int VEC, int OPT, typename... BagP>
 __global__ __launch_bounds__(WAVES * WAVE) void sparse_apply_kernel(
     float* __restrict__ table, const long* __restrict__ sorted,
     const long* __restrict__ perm, const G* __restrict__ grads,
     const float* __restrict__ scratch, float* __restrict__ s1,
     float* __restrict__ s2, bf16_t* __restrict__ shadow, long n, int D,
-    long V, SparseHp hp) {
+    long V, SparseHp hp, BagP... bagp) {
   const int lane = threadIdx.x & (WAVE - 1);
   const long base = ((long)blockIdx.x * WAVES + (threadIdx.x >> 6)) * WAVE;
   const long i = base + lane;
@@ -248,7 +294,7 @@ __global__ __launch_bounds__(WAVES * WAVE) void sparse_apply_kernel(
       for (int e = 0; e < VEC; ++e) g[e] = 0.f;
       if (!is_long) {
         sum_run<G, VEC>(sorted, perm, grads, n, pos, CHUNK, id, D, col,
-                        active, lane, g);
+                        active, lane, g, bagp...);
       } else {
         // partial sums of pass 1, added in chunk order
         long slot = pos / SLOT_DIV;
@@ -274,20 +320,42 @@ __global__ __launch_bounds__(WAVES * WAVE) void sparse_apply_kernel(
   }
 }
 
-template <typename G, int VEC>
+// Bag mode's expansion: one wave per bag writes, for each of its
+// positions, the bag's row number and the coefficient c_i (bag.h), after
+// reducing W_b for mean. Unweighted bags read no weights. bag_of / coef
+// arrive zeroed, so a position no bag covers (an offsets contract
+// violation) contributes 0 * grads[0].
+__global__ __launch_bounds__(WAVES * WAVE) void bag_expand_kernel(
+    const long* __restrict__ offsets, const float* __restrict__ weights,
+    int* __restrict__ bag_of, float* __restrict__ coef, long B, long n,
+    int mean) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const long b = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (b >= B) return;   // wave-uniform
+  long s, e;
+  bag_range(offsets, b, n, s, e);
+  const float W = mean ? bag_weight_sum(weights, s, e, lane) : 0.f;
+  for (long p = s + lane; p < e; p += WAVE) {
+    bag_of[p] = (int)b;
+    coef[p] = bag_coef(weights ? weights[p] : 1.f, W, mean != 0);
+  }
+}
+
+template <typename G, int VEC, typename... BagP>
 void launch_typed(int opt, float* table, const long* sorted, const long* perm,
                   const G* grads, float* scratch, float* s1, float* s2,
                   bf16_t* shadow, long n, int D, long V, const SparseHp& hp,
-                  hipStream_t stream) {
+                  hipStream_t stream, BagP... bagp) {
   const dim3 block(WAVES * WAVE);
   const dim3 grid((unsigned)((n + WAVES * WAVE - 1) / (WAVES * WAVE)));
   if (n > CHUNK)
-    hipLaunchKernelGGL((sparse_partial_kernel<G, VEC>), grid, block, 0,
-                       stream, sorted, perm, grads, scratch, n, D, V);
+    hipLaunchKernelGGL((sparse_partial_kernel<G, VEC, BagP...>), grid, block,
+                       0, stream, sorted, perm, grads, scratch, n, D, V,
+                       bagp...);
 #define DISP(OPTV)                                                          \
-  hipLaunchKernelGGL((sparse_apply_kernel<G, VEC, OPTV>), grid, block, 0,   \
-                     stream, table, sorted, perm, grads, scratch, s1, s2,   \
-                     shadow, n, D, V, hp)
+  hipLaunchKernelGGL((sparse_apply_kernel<G, VEC, OPTV, BagP...>), grid,    \
+                     block, 0, stream, table, sorted, perm, grads, scratch, \
+                     s1, s2, shadow, n, D, V, hp, bagp...)
   switch (opt) {
     case SPARSE_SGD: DISP(SPARSE_SGD); break;
     case SPARSE_SGD_MOM: DISP(SPARSE_SGD_MOM); break;
@@ -295,6 +363,34 @@ void launch_typed(int opt, float* table, const long* sorted, const long* perm,
     default: DISP(SPARSE_ADAM); break;
   }
 #undef DISP
+}
+
+template <typename... BagP>
+void launch_any(int opt, float* table, const long* sorted, const long* perm,
+                const void* grads, bool g_bf16, float* scratch, float* s1,
+                float* s2, bf16_t* shadow, long n, int D, long V,
+                const SparseHp& hp, hipStream_t stream, BagP... bagp) {
+  // vector path needs 16-byte aligned rows: D % 4 == 0 and aligned bases
+  // (a view at a storage offset can break the latter)
+  const uintptr_t bases = (uintptr_t)table | (uintptr_t)grads |
+                          (uintptr_t)scratch | (uintptr_t)s1 |
+                          (uintptr_t)s2 | (uintptr_t)shadow;
+  const bool vec = (D % 4) == 0 && (bases % 16) == 0;
+  if (g_bf16) {
+    if (vec) launch_typed<bf16_t, 4>(opt, table, sorted, perm,
+                                     (const bf16_t*)grads, scratch, s1, s2,
+                                     shadow, n, D, V, hp, stream, bagp...);
+    else launch_typed<bf16_t, 1>(opt, table, sorted, perm,
+                                 (const bf16_t*)grads, scratch, s1, s2,
+                                 shadow, n, D, V, hp, stream, bagp...);
+  } else {
+    if (vec) launch_typed<float, 4>(opt, table, sorted, perm,
+                                    (const float*)grads, scratch, s1, s2,
+                                    shadow, n, D, V, hp, stream, bagp...);
+    else launch_typed<float, 1>(opt, table, sorted, perm,
+                                (const float*)grads, scratch, s1, s2, shadow,
+                                n, D, V, hp, stream, bagp...);
+  }
 }
 
 }  // namespace
@@ -310,25 +406,28 @@ void launch_sparse_apply(int opt, float* table, const long* sorted,
                          float* scratch, float* s1, float* s2, bf16_t* shadow,
                          long n, int D, long V, const SparseHp& hp,
                          hipStream_t stream) {
-  // vector path needs 16-byte aligned rows: D % 4 == 0 and aligned bases
-  // (a view at a storage offset can break the latter)
-  const uintptr_t bases = (uintptr_t)table | (uintptr_t)grads |
-                          (uintptr_t)scratch | (uintptr_t)s1 |
-                          (uintptr_t)s2 | (uintptr_t)shadow;
-  const bool vec = (D % 4) == 0 && (bases % 16) == 0;
-  if (g_bf16) {
-    if (vec) launch_typed<bf16_t, 4>(opt, table, sorted, perm,
-                                     (const bf16_t*)grads, scratch, s1, s2,
-                                     shadow, n, D, V, hp, stream);
-    else launch_typed<bf16_t, 1>(opt, table, sorted, perm,
-                                 (const bf16_t*)grads, scratch, s1, s2,
-                                 shadow, n, D, V, hp, stream);
-  } else {
-    if (vec) launch_typed<float, 4>(opt, table, sorted, perm,
-                                    (const float*)grads, scratch, s1, s2,
-                                    shadow, n, D, V, hp, stream);
-    else launch_typed<float, 1>(opt, table, sorted, perm,
-                                (const float*)grads, scratch, s1, s2, shadow,
-                                n, D, V, hp, stream);
-  }
+  launch_any(opt, table, sorted, perm, grads, g_bf16, scratch, s1, s2, shadow,
+             n, D, V, hp, stream);
+}
+
+// offsets [B+1] (+ weights [n] or null) -> bag_of / coef [n], both zeroed
+// by the caller. B, n > 0.
+void launch_bag_expand(const long* offsets, const float* weights, int* bag_of,
+                       float* coef, long B, long n, bool mean,
+                       hipStream_t stream) {
+  const dim3 grid((unsigned)((B + WAVES - 1) / WAVES));
+  hipLaunchKernelGGL(bag_expand_kernel, grid, dim3(WAVES * WAVE), 0, stream,
+                     offsets, weights, bag_of, coef, B, n, (int)mean);
+}
+
+// launch_sparse_apply with grads = [B,D] bag gradients and the per-position
+// bag_of / coef of launch_bag_expand.
+void launch_sparse_apply_bag(int opt, float* table, const long* sorted,
+                             const long* perm, const void* grads, bool g_bf16,
+                             const int* bag_of, const float* coef,
+                             float* scratch, float* s1, float* s2,
+                             bf16_t* shadow, long n, int D, long V,
+                             const SparseHp& hp, hipStream_t stream) {
+  launch_any(opt, table, sorted, perm, grads, g_bf16, scratch, s1, s2, shadow,
+             n, D, V, hp, stream, BagIdx{bag_of, coef});
 }

@@ -11,6 +11,14 @@ gradients back:
 
 * **pull**: worker sends the id vector, the PS gathers bf16 rows with
   the HIP gather kernel (``csrc/embedding.hip``) and sends them back;
+* **pooled pull / push** (``pull_pooled`` / ``push_pooled``): the lookup
+  of recommender and CTR models — a feature is a variable-length bag of
+  ids whose rows are summed or averaged (TF's ``embedding_lookup_sparse``,
+  optional per-id weights). The worker sends CSR (ids, offsets[, weights]);
+  the PS reduces each bag with the HIP ``embedding_bag`` kernel and answers
+  with ONE row per bag, and a push carries ONE gradient row per bag that
+  the fused sparse-apply kernel reads through a bag indirection: both
+  directions move B x D instead of n x D.
 * **push**: worker sends (ids, row grads); the PS applies SGD by
   scatter-adding ``-lr * grad`` into the fp32 master with the HIP
   scatter-add kernel (duplicate ids accumulate, matching TF's
@@ -43,6 +51,22 @@ import torch.distributed as dist
 
 from tfmesos_amd import ops
 from tfmesos_amd.ps.chan import Chan, make_pair_chans  # noqa: F401
+
+
+# Wire format. Every request starts with a 2-int64 header [count, word]
+# (the size of the server's posted irecv). Row requests, unchanged: count
+# > 0 pulls count ids, count < 0 pushes |count| id/grad rows, count == 0
+# is the worker's done marker; word = table index. Pooled requests set
+# kind 1 in word's upper half and count = +-(n + 1) (never 0, so an n == 0
+# request cannot pass for the done marker); a second 2-int64 header
+# [B, flags] follows, then ids [n], offsets [B+1], weights [n] if flagged,
+# and for a push the bf16 [B,D] bag gradients. Zero-size tensors are not
+# sent. A pooled pull answers with bf16 [B,D]: the link carries
+# 8n + 8(B+1) (+ 4n) + 2BD bytes instead of 8n + 2nD.
+_KIND_SHIFT = 32
+_KIND_POOLED = 1
+_COMBINERS = ("sum", "mean")    # flags bit 0
+_HAS_WEIGHTS = 2                # flags bit 1
 
 
 class EmbeddingTable(object):
@@ -120,7 +144,8 @@ class EmbeddingTable(object):
             self.shadow.index_copy_(
                 0, uniq, self.master.index_select(0, uniq).to(torch.bfloat16))
 
-    def _push_fused(self, ids, grads, lr):
+    def _push_fused(self, ids, grads, lr, **bag):
+        """bag: offsets/weights/combiner of a pooled push (grads [B,D])."""
         hp, st = self.hparams, self.state
         self.step += 1
         if self.optimizer == "sgd":
@@ -128,18 +153,41 @@ class EmbeddingTable(object):
                            momentum=hp["momentum"],
                            momentum_buf=st.get("momentum_buf"),
                            weight_decay=hp["weight_decay"],
-                           bf16_out=self.shadow)
+                           bf16_out=self.shadow, **bag)
         elif self.optimizer == "adagrad":
             ops.sparse_adagrad(self.master, ids, grads, st["accum"], lr,
                                eps=hp["eps"],
                                weight_decay=hp["weight_decay"],
-                               bf16_out=self.shadow)
+                               bf16_out=self.shadow, **bag)
         else:
             ops.sparse_adam(self.master, ids, grads, st["exp_avg"],
                             st["exp_avg_sq"], self.step, lr,
                             beta1=hp["beta1"], beta2=hp["beta2"],
                             eps=hp["eps"], weight_decay=hp["weight_decay"],
-                            bf16_out=self.shadow)
+                            bf16_out=self.shadow, **bag)
+
+    def pull_pooled(self, ids, offsets, weights=None, combiner="sum"):
+        """bf16 [B,D] pooled rows from the shadow: bag b (positions
+        [offsets[b], offsets[b+1]) of ids) summed or averaged, with
+        optional per-id weights (``ops.embedding_bag``)."""
+        with self.lock:
+            return ops.embedding_bag(self.shadow, ids, offsets,
+                                     weights=weights, combiner=combiner)
+
+    def push_pooled(self, ids, offsets, bag_grads, weights=None,
+                    combiner="sum", lr=None):
+        """Sparse apply of one pooled push: position i of bag b contributes
+        c_i * bag_grads[b] (bag_grads [B,D] bf16 or fp32); duplicates sum
+        and the optimizer runs once per touched row, as for ``push``.
+
+        Always the fused sparse-apply kernel, also for a plain-SGD table
+        built with ``fused_apply=False``: the scatter-add path would need
+        the expanded n x D rows this call exists to avoid. ``step``
+        advances once per push."""
+        lr = self.lr if lr is None else lr
+        with self.lock:
+            self._push_fused(ids, bag_grads, lr, offsets=offsets,
+                             weights=weights, combiner=combiner)
 
     def state_dict(self):
         """Master, optimizer state and step (CPU copies) — a table
@@ -221,6 +269,54 @@ class SparseWorkerClient(object):
                       if h == self.homes[name])
         return mine.index(name)
 
+    def _send_pooled(self, c, name, sign, ids, offsets, weights, combiner):
+        """Headers and index tensors of a pooled request (see
+        ``_pooled_hdr``). Returns B."""
+        if combiner not in _COMBINERS:
+            raise ValueError("unknown combiner %r (have %s)"
+                             % (combiner, list(_COMBINERS)))
+        ids = ids.to(self.device)
+        if weights is not None and tuple(weights.shape) != (ids.numel(),):
+            raise ValueError("weights must be [n] = [%d]" % ids.numel())
+        nbags = offsets.numel() - 1
+        flags = _COMBINERS.index(combiner) | \
+            (_HAS_WEIGHTS if weights is not None else 0)
+        c.send(self._hdr(sign * (ids.numel() + 1),
+                         self._tidx(name) | _KIND_POOLED << _KIND_SHIFT))
+        c.send(self._hdr(nbags, flags))
+        if ids.numel():     # no zero-size messages: the server skips them too
+            c.send(ids)
+        c.send(offsets.to(device=self.device, dtype=torch.int64))
+        if weights is not None and ids.numel():
+            c.send(weights.to(device=self.device, dtype=torch.float32))
+        return nbags
+
+    def pull_pooled(self, name, ids, offsets, weights=None, combiner="sum"):
+        """bf16 [B,D] pooled rows: the PS gathers and reduces each bag
+        (``EmbeddingTable.pull_pooled``), so the link carries B x D bf16
+        instead of n x D."""
+        c = self._chan(name)
+        rows = torch.empty(offsets.numel() - 1, self.dims[name],
+                           dtype=torch.bfloat16, device=self.device)
+        if rows.shape[0] == 0:      # no bags: nothing to ask for
+            return rows
+        self._send_pooled(c, name, 1, ids, offsets, weights, combiner)
+        c.recv_into(rows)
+        return rows
+
+    def push_pooled(self, name, ids, offsets, bag_grads, weights=None,
+                    combiner="sum"):
+        """Push [B,D] bag gradients (sent as bf16); the PS applies
+        c_i * bag_grads[b] per position (``EmbeddingTable.push_pooled``)."""
+        c = self._chan(name)
+        if bag_grads.dim() != 2 or bag_grads.shape[0] != offsets.numel() - 1:
+            raise ValueError("bag_grads must be [B,D] = [%d,D], got %s"
+                             % (offsets.numel() - 1, tuple(bag_grads.shape)))
+        if bag_grads.numel() == 0:      # no bags: nothing to push
+            return
+        self._send_pooled(c, name, -1, ids, offsets, weights, combiner)
+        c.send(bag_grads.to(device=self.device, dtype=torch.bfloat16))
+
     def pull_many(self, reqs):
         """Concurrent pulls from multiple PS ranks: issue every
         request's sends and row-irecvs before waiting (the sequential
@@ -284,8 +380,9 @@ class SparseWorkerClient(object):
 
 class SparsePSServer(object):
     """PS-side server, fixed request protocol (n>0: pull n ids; n<0:
-    push |n| id/grad rows; n==0: worker done). Exits when every worker
-    has sent done.
+    push |n| id/grad rows; n==0: worker done; pooled pulls and pushes
+    carry kind 1 in the header's second word — see the wire format at the
+    top of this module). Exits when every worker has sent done.
 
     Serving strategy by backend (same rationale as AsyncPSServer):
     nccl/RCCL = ONE polling loop over irecv'd headers (CUDA-event
@@ -306,7 +403,11 @@ class SparsePSServer(object):
         count = int(hdr[0].item())
         if count == 0:
             return False
-        table = self.tables[names[int(hdr[1].item())]]
+        word = int(hdr[1].item())
+        table = self.tables[names[word & ((1 << _KIND_SHIFT) - 1)]]
+        if word >> _KIND_SHIFT == _KIND_POOLED:
+            self._handle_pooled(c, hdr, table, count)
+            return True
         ids = c.recv_new((abs(count),), torch.int64, table.device)
         if count > 0:
             c.send(table.pull(ids))
@@ -315,6 +416,26 @@ class SparsePSServer(object):
                                table.device)
             table.push(ids, grads)
         return True
+
+    def _handle_pooled(self, c, hdr, table, count):
+        """One pooled request (count = +-(n + 1)); the second header is
+        received where the first one lives (device-resident under RCCL)."""
+        n, dev = abs(count) - 1, table.device
+        hdr2 = c.recv_new((2,), torch.int64, hdr.device)
+        nbags, flags = int(hdr2[0].item()), int(hdr2[1].item())
+        combiner = _COMBINERS[flags & 1]
+        ids = c.recv_new((n,), torch.int64, dev) if n else \
+            torch.empty(0, dtype=torch.int64, device=dev)
+        offsets = c.recv_new((nbags + 1,), torch.int64, dev)
+        weights = None
+        if flags & _HAS_WEIGHTS:
+            weights = c.recv_new((n,), torch.float32, dev) if n else \
+                torch.empty(0, device=dev)
+        if count > 0:
+            c.send(table.pull_pooled(ids, offsets, weights, combiner))
+        else:
+            grads = c.recv_new((nbags, table.dim), torch.bfloat16, dev)
+            table.push_pooled(ids, offsets, grads, weights, combiner)
 
     def serve(self):
         import torch.distributed as dist
