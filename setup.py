@@ -26,6 +26,7 @@ sources = [
     os.path.join(CSRC, "embedding.hip"),
     os.path.join(CSRC, "embedding_bag.hip"),
     os.path.join(CSRC, "sparse_apply.hip"),
+    os.path.join(CSRC, "partition.hip"),
     os.path.join(CSRC, "elementwise.hip"),
 ]
 

@@ -15,8 +15,12 @@ apply for embedding rows (sparse_sgd / sparse_adagrad / sparse_adam —
 TF's SparseApply*: duplicates summed, one update per touched row), and
 pooled (bag) lookups: embedding_bag forward (TF's embedding_lookup_sparse,
 combiner sum / mean, optional weights) and the same sparse applies fed
-bag gradients (``offsets=``).
+bag gradients (``offsets=``); and the routing of requests to a row-sharded
+table (TF's partitioned variable): shard_partition, permute_rows,
+shard_bag_offsets, bag_coefficients.
 """
+
+import collections
 
 import torch
 
@@ -404,6 +408,159 @@ def embedding_bag(table, ids, offsets, weights=None, combiner="sum",
     out = torch.zeros(offsets.numel() - 1, table.shape[1])
     out.index_add_(0, bag_of[keep], c[keep, None] * rows)
     return out.to(out_dtype)
+
+
+# ----------------------------------------------- row-sharded table routing
+#
+# A table of V rows split by row over S shards (TF's partitioned variable,
+# partition_strategy "mod" or "div"):
+#   mod: shard = id % S, local = id // S;
+#   div: q, x = divmod(V, S); the first x shards hold q+1 rows, the rest q;
+#        shard = max(id // (q+1), (id - x) // q), local = id - start(shard).
+# An id outside [0, V) goes to shard 0 with local = -1: out of range on
+# every shard, so it behaves as on an unsharded table. GPU: csrc/
+# partition.hip — no atomics, bit-reproducible, nothing read back.
+
+ShardPartition = collections.namedtuple(
+    "ShardPartition", ["local", "perm", "inv", "starts"])
+ShardPartition.__doc__ = """Stable partition of a request's ids by shard.
+
+local [n]: shard-local ids grouped by shard, original order inside a shard;
+perm [n]: the original position held by each slot; inv [n]: the slot of
+each original position; starts [S+1]: shard s owns slots
+[starts[s], starts[s+1])."""
+
+_STRATEGIES = ("mod", "div")
+
+
+def _shard_check(rows, num_shards, strategy):
+    if strategy not in _STRATEGIES:
+        raise ValueError("unknown partition strategy %r (have %s)"
+                         % (strategy, list(_STRATEGIES)))
+    if not 1 <= num_shards <= 64:
+        raise ValueError("num_shards must be in [1, 64], got %r"
+                         % (num_shards,))
+    if rows < num_shards:
+        raise ValueError("a table of %d rows cannot be split over %d shards"
+                         % (rows, num_shards))
+
+
+def shard_rows(rows, num_shards, shard, strategy="mod"):
+    """Row count of shard ``shard`` of a ``rows``-row table."""
+    return len(shard_global_ids(rows, num_shards, shard, strategy))
+
+
+def shard_global_ids(rows, num_shards, shard, strategy="mod"):
+    """The global ids shard ``shard`` holds, in local order (a range)."""
+    _shard_check(rows, num_shards, strategy)
+    if not 0 <= shard < num_shards:
+        raise ValueError("shard must be in [0, %d), got %r"
+                         % (num_shards, shard))
+    if strategy == "mod":
+        return range(shard, rows, num_shards)
+    q, x = divmod(rows, num_shards)
+    start = shard * q + min(shard, x)
+    return range(start, start + q + (1 if shard < x else 0))
+
+
+def _route_cpu(ids, rows, num_shards, strategy):
+    """(shard, local) per id, by the rule above."""
+    valid = (ids >= 0) & (ids < rows)
+    safe = torch.where(valid, ids, torch.zeros_like(ids))
+    if strategy == "mod":
+        shard = safe % num_shards
+        local = torch.div(safe, num_shards, rounding_mode="floor")
+    else:
+        q, x = divmod(rows, num_shards)
+        shard = torch.maximum(
+            torch.div(safe, q + 1, rounding_mode="floor"),
+            torch.div(safe - x, q, rounding_mode="floor"))
+        local = safe - (shard * q + torch.clamp(shard, max=x))
+    return (torch.where(valid, shard, torch.zeros_like(ids)),
+            torch.where(valid, local, torch.full_like(ids, -1)))
+
+
+@torch.no_grad()
+def shard_partition(ids, rows, num_shards, strategy="mod"):
+    """Stable partition of ids int64 [n] (n < 2**31) by owning shard ->
+    ShardPartition. GPU: count / scan / scatter (csrc/partition.hip; the
+    scan is torch.cumsum), no host sync. CPU: a stable sort of the shard
+    numbers."""
+    _shard_check(rows, num_shards, strategy)
+    if ids.dim() != 1 or ids.dtype != torch.int64:
+        raise ValueError("ids must be int64 [n]")
+    if ids.numel() >= 2 ** 31:
+        raise ValueError("shard_partition: n must be below 2**31")
+    if ids.is_cuda:
+        return ShardPartition(*_ext().shard_partition(
+            ids.contiguous(), int(rows), int(num_shards), strategy == "div"))
+    shard, local = _route_cpu(ids, rows, num_shards, strategy)
+    perm = torch.sort(shard, stable=True)[1]
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(ids.numel())
+    starts = torch.zeros(num_shards + 1, dtype=torch.int64)
+    starts[1:] = torch.bincount(shard, minlength=num_shards).cumsum(0)
+    return ShardPartition(local[perm], perm, inv, starts)
+
+
+@torch.no_grad()
+def permute_rows(rows, perm, out_dtype=None):
+    """out[j] = rows[perm[j]] cast to out_dtype (default: rows' dtype);
+    rows [n,D] fp32 or bf16, out fp32 or bf16: a push's gradient rows laid
+    out in wire order and wire dtype in one pass."""
+    out_dtype = rows.dtype if out_dtype is None else out_dtype
+    ok = (torch.float32, torch.bfloat16)
+    if rows.dim() != 2 or rows.dtype not in ok or out_dtype not in ok:
+        raise ValueError("permute_rows: rows must be [n,D] fp32 or bf16 and "
+                         "out_dtype fp32 or bf16")
+    if rows.is_cuda:
+        return _ext().permute_rows(rows.contiguous(), perm.contiguous(),
+                                   out_dtype == torch.bfloat16)
+    return rows.index_select(0, perm).to(out_dtype)
+
+
+@torch.no_grad()
+def shard_bag_offsets(perm, starts, offsets):
+    """shard_offsets int64 [S, B+1] of a bagged request (offsets [B+1])
+    after shard_partition: the stable partition keeps each bag contiguous
+    inside each shard, and shard_offsets[s][b] is the number of shard s's
+    slots whose original position lies before offsets[b]."""
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("offsets must be int64 [B+1]")
+    if perm.is_cuda:
+        return _ext().shard_bag_offsets(perm.contiguous(),
+                                        starts.contiguous(),
+                                        offsets.contiguous())
+    S = starts.numel() - 1
+    out = torch.empty(S, offsets.numel(), dtype=torch.int64)
+    off = offsets.clamp(0, perm.numel())
+    for s in range(S):
+        seg = perm[int(starts[s]):int(starts[s + 1])]
+        out[s] = torch.searchsorted(seg, off)
+    return out
+
+
+@torch.no_grad()
+def bag_coefficients(n, offsets, weights=None, combiner="sum"):
+    """c fp32 [n]: the coefficient of every position of a bagged request
+    (rule above: w_i, or w_i / W_b for mean, 0 when W_b == 0), 0 for a
+    position no bag covers. On the GPU the bits equal what embedding_bag
+    and the pooled sparse applies compute internally (csrc/bag.h), so
+    passing c as ``weights`` with combiner "sum" reproduces a "mean"
+    call bit for bit."""
+    if combiner not in ("sum", "mean"):
+        raise ValueError("unknown combiner %r (have 'sum', 'mean')"
+                         % (combiner,))
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("offsets must be int64 [B+1]")
+    if weights is not None and tuple(weights.shape) != (n,):
+        raise ValueError("weights must be [n] = [%d], got %s"
+                         % (n, tuple(weights.shape)))
+    if offsets.is_cuda:
+        return _ext().bag_coefficients(
+            int(n), offsets.contiguous(),
+            _bag_weights(weights, offsets.device), combiner == "mean")
+    return _bag_expand_cpu(torch.empty(n), offsets, weights, combiner)[1]
 
 
 # ------------------------------------------------- sparse optimizer applies

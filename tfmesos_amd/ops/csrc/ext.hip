@@ -58,6 +58,17 @@ void launch_scatter_add_f32(float*, const long*, const float*, long, int,
 void launch_embedding_bag(const void*, bool, const long*, const long*,
                           const float*, void*, bool, long, long, int, long,
                           bool, hipStream_t);
+long shard_windows(long);
+void launch_shard_count(const long*, int*, long, long, int, bool,
+                        hipStream_t);
+void launch_shard_scatter(const long*, const long*, long*, long*, long*,
+                          long*, long, long, int, bool, hipStream_t);
+void launch_permute_rows(const void*, bool, const long*, void*, bool, long,
+                         long, int, hipStream_t);
+void launch_shard_bag_offsets(const long*, const long*, const long*, long*,
+                              long, long, int, hipStream_t);
+void launch_bag_coef(const long*, const float*, float*, long, long, bool,
+                     hipStream_t);
 void launch_relu_bwd(const bf16_t*, const bf16_t*, bf16_t*, long,
                      hipStream_t);
 void launch_add_n(const bf16_t* const*, int, bf16_t*, long, hipStream_t);
@@ -937,6 +948,113 @@ void sparse_apply_bag(torch::Tensor table, torch::Tensor ids,
                           scratch_p, s1, s2, shp, n, D, V, hp, cur_stream());
 }
 
+// Stable partition of ids by owning shard (partition.hip): count kernel,
+// cumsum of the per-window counts (plumbing; stays on the device), scatter
+// kernel. Returns local, perm, inv [n] and starts [S+1]; no host sync.
+std::vector<torch::Tensor> shard_partition(torch::Tensor ids, long rows,
+                                           long num_shards, bool div) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == torch::kInt64 &&
+              ids.dim() == 1 && ids.is_contiguous(),
+              "shard_partition: ids must be contiguous i64 [n] on GPU");
+  TORCH_CHECK(num_shards >= 1 && num_shards <= 64 && rows >= num_shards,
+              "shard_partition: need 1 <= num_shards <= 64 and "
+              "rows >= num_shards");
+  const long n = ids.numel();
+  TORCH_CHECK(n < (long)INT_MAX, "shard_partition: n must be below 2^31");
+  const int S = (int)num_shards;
+  auto opt = ids.options();
+  auto local = torch::empty({n}, opt), perm = torch::empty({n}, opt);
+  auto inv = torch::empty({n}, opt);
+  if (n == 0)   // a zero-size grid is a launch error
+    return {local, perm, inv, torch::zeros({S + 1}, opt)};
+  auto starts = torch::empty({S + 1}, opt);
+  auto counts = torch::empty({S * shard_windows(n)},
+                             opt.dtype(torch::kInt32));
+  launch_shard_count(ids.data_ptr<long>(), counts.data_ptr<int>(), n, rows, S,
+                     div, cur_stream());
+  auto incl = torch::cumsum(counts, 0, torch::kInt64);
+  launch_shard_scatter(ids.data_ptr<long>(), incl.data_ptr<long>(),
+                       local.data_ptr<long>(), perm.data_ptr<long>(),
+                       inv.data_ptr<long>(), starts.data_ptr<long>(), n, rows,
+                       S, div, cur_stream());
+  return {local, perm, inv, starts};
+}
+
+// out[j] = cast(rows[perm[j]]): a push's gradient rows in wire order and
+// wire dtype in one pass. A perm entry outside [0, n_rows) gives a zero row.
+torch::Tensor permute_rows(torch::Tensor rows, torch::Tensor perm,
+                           bool out_bf16) {
+  TORCH_CHECK(rows.is_cuda() && rows.dim() == 2 && rows.is_contiguous(),
+              "permute_rows: rows must be contiguous [n,D] on GPU");
+  const bool r_bf16 = rows.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(r_bf16 || rows.scalar_type() == torch::kFloat32,
+              "permute_rows: rows must be bf16 or fp32");
+  TORCH_CHECK(perm.is_cuda() && perm.scalar_type() == torch::kInt64 &&
+              perm.dim() == 1 && perm.is_contiguous(),
+              "permute_rows: perm must be contiguous i64 [m] on GPU");
+  const long m = perm.numel(), D = rows.size(1);
+  TORCH_CHECK(D <= (long)INT_MAX && (m + 3) / 4 < (long)INT_MAX,
+              "permute_rows: too large for one grid");
+  auto out = torch::empty({m, D},
+                          rows.options().dtype(out_bf16 ? torch::kBFloat16
+                                                        : torch::kFloat32));
+  if (m == 0 || D == 0) return out;
+  launch_permute_rows(rows.data_ptr(), r_bf16, perm.data_ptr<long>(),
+                      out.data_ptr(), out_bf16, m, rows.size(0), (int)D,
+                      cur_stream());
+  return out;
+}
+
+// shard_offsets [S, B+1]: the CSR of a bagged request inside each shard's
+// slice of the partition.
+torch::Tensor shard_bag_offsets(torch::Tensor perm, torch::Tensor starts,
+                                torch::Tensor offsets) {
+  auto ok = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.scalar_type() == torch::kInt64 && t.dim() == 1 &&
+           t.is_contiguous();
+  };
+  TORCH_CHECK(ok(perm) && ok(starts) && ok(offsets),
+              "shard_bag_offsets: perm, starts, offsets must be contiguous "
+              "i64 vectors on GPU");
+  TORCH_CHECK(starts.numel() >= 2 && starts.numel() <= 65 &&
+              offsets.numel() >= 1, "shard_bag_offsets: starts must be "
+              "[S+1], 1 <= S <= 64, offsets [B+1]");
+  const long S = starts.numel() - 1, B = offsets.numel() - 1;
+  TORCH_CHECK(S * (B + 1) / 256 < (long)INT_MAX,
+              "shard_bag_offsets: too many bags");
+  auto out = torch::empty({S, B + 1}, perm.options());
+  launch_shard_bag_offsets(perm.data_ptr<long>(), starts.data_ptr<long>(),
+                           offsets.data_ptr<long>(), out.data_ptr<long>(),
+                           perm.numel(), B, (int)S, cur_stream());
+  return out;
+}
+
+// c [n] fp32: the per-position coefficients of bag.h.
+torch::Tensor bag_coefficients(long n, torch::Tensor offsets,
+                               torch::Tensor weights, bool mean) {
+  TORCH_CHECK(offsets.is_cuda() && offsets.scalar_type() == torch::kInt64 &&
+              offsets.dim() == 1 && offsets.numel() >= 1 &&
+              offsets.is_contiguous(),
+              "bag_coefficients: offsets must be contiguous i64 [B+1] on GPU");
+  TORCH_CHECK(n >= 0 && offsets.numel() - 1 <= (long)INT_MAX,
+              "bag_coefficients: bad n or too many bags");
+  const float* w = nullptr;
+  if (weights.numel() > 0) {
+    TORCH_CHECK(weights.is_cuda() &&
+                weights.scalar_type() == torch::kFloat32 &&
+                weights.is_contiguous() && weights.numel() == n,
+                "bag_coefficients: weights must be contiguous fp32 [n] on "
+                "GPU");
+    w = weights.data_ptr<float>();
+  }
+  const long B = offsets.numel() - 1;
+  auto coef = torch::zeros({n}, offsets.options().dtype(torch::kFloat32));
+  if (n == 0 || B == 0) return coef;
+  launch_bag_coef(offsets.data_ptr<long>(), w, coef.data_ptr<float>(), B, n,
+                  mean, cur_stream());
+  return coef;
+}
+
 torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor act) {
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16 &&
               dy.is_contiguous() && act.is_contiguous() &&
@@ -1564,6 +1682,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("step"), py::arg("mean"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
         py::arg("grad_scale"));
+  m.def("shard_partition", &shard_partition,
+        "stable partition of ids by owning shard: local, perm, inv, starts",
+        py::arg("ids"), py::arg("rows"), py::arg("num_shards"),
+        py::arg("div"));
+  m.def("permute_rows", &permute_rows, "out[j] = cast(rows[perm[j]])",
+        py::arg("rows"), py::arg("perm"), py::arg("out_bf16"));
+  m.def("shard_bag_offsets", &shard_bag_offsets,
+        "per-shard CSR offsets [S,B+1] of a partitioned bagged request",
+        py::arg("perm"), py::arg("starts"), py::arg("offsets"));
+  m.def("bag_coefficients", &bag_coefficients,
+        "per-position bag coefficients c [n]",
+        py::arg("n"), py::arg("offsets"), py::arg("weights"),
+        py::arg("mean"));
   m.def("relu_bwd", &relu_bwd);
   m.def("colsum", &colsum, py::arg("x"), py::arg("out"));
 }

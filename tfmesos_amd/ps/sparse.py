@@ -3,11 +3,12 @@ torch.distributed (RCCL/xGMI on GPU, gloo on CPU).
 
 The reference's PS architecture implies sparse variable traffic (row
 factors in ``examples/matrix_factorization.py``; TF's PS gathers
-embedding rows on pull and scatter-adds gradients on push). Here each
-named table lives on ONE ps rank (manual model parallelism, like W on
-ps:0 / H on ps:1 in the reference, ``matrix_factorization.py:21-28``);
-workers pull only the rows a minibatch touches and push sparse row
-gradients back:
+embedding rows on pull and scatter-adds gradients on push). A named
+table lives on ONE ps rank (manual model parallelism, like W on
+ps:0 / H on ps:1 in the reference, ``matrix_factorization.py:21-28``) or
+is split BY ROW over several (TF's partitioned variable, strategy "mod"
+or "div" — see "Row-sharded tables" below); workers pull only the rows a
+minibatch touches and push sparse row gradients back:
 
 * **pull**: worker sends the id vector, the PS gathers bf16 rows with
   the HIP gather kernel (``csrc/embedding.hip``) and sends them back;
@@ -41,6 +42,20 @@ memory, for CPU clusters and tests.
 The PS serves ALL workers from ONE polling loop (irecv on each
 channel's header): single-threaded by design, since N threads blocking
 on N RCCL communicators of one device can deadlock.
+
+Row-sharded tables. ``table_homes[name]`` may be a list of distinct PS
+ranks: shard ``s`` (an ``EmbeddingTable.shard_of``) lives on
+``homes[s]``. The worker routes every request on its own device
+(``_ShardRoute``: ``ops.shard_partition`` — a STABLE partition of the ids
+by owning shard —, ``ops.permute_rows`` for the gradient rows,
+``ops.shard_bag_offsets`` / ``ops.bag_coefficients`` for bags; HIP
+kernels of ``csrc/partition.hip``), posts every shard's sends and
+receives before waiting on any, and stitches the answers back into
+request order. Because the partition is stable, every row sees its
+contributions in the order an unsharded table would, so the shards end
+bit-identical to the unsharded table. One device->host copy per request
+is unavoidable: the message sizes are the shard counts (``starts``).
+``ShardedEmbeddingTable`` runs the same routing over local shards.
 """
 
 import threading
@@ -62,11 +77,23 @@ from tfmesos_amd.ps.chan import Chan, make_pair_chans  # noqa: F401
 # [B, flags] follows, then ids [n], offsets [B+1], weights [n] if flagged,
 # and for a push the bf16 [B,D] bag gradients. Zero-size tensors are not
 # sent. A pooled pull answers with bf16 [B,D]: the link carries
-# 8n + 8(B+1) (+ 4n) + 2BD bytes instead of 8n + 2nD.
+# 8n + 8(B+1) (+ 4n) + 2BD bytes instead of 8n + 2nD. With flags bit 2 the
+# answer is fp32 [B,D]: the partial sums of a row-sharded table's pooled
+# pull travel unrounded, so that the worker's sum over the shards is
+# rounded to bf16 ONCE, like an unsharded table's bag (a bf16 partial would
+# cost 2**-8 relative per shard before the final rounding).
+# Kind 2 is a row request with count = +-(n + 1): ids [n], then for a push
+# bf16 [n,D] gradients, for a pull the bf16 [n,D] answer; zero-size tensors
+# are not sent. It exists because kind 0 cannot say "push of zero rows":
+# a row push to a sharded table goes to EVERY shard, also one that gets no
+# ids, so that each shard's ``step`` (Adam's bias correction) advances as
+# an unsharded table's would.
 _KIND_SHIFT = 32
 _KIND_POOLED = 1
+_KIND_ROWS = 2
 _COMBINERS = ("sum", "mean")    # flags bit 0
 _HAS_WEIGHTS = 2                # flags bit 1
+_OUT_F32 = 4                    # flags bit 2 (pooled pull: fp32 answer)
 
 
 class EmbeddingTable(object):
@@ -111,9 +138,7 @@ class EmbeddingTable(object):
         self.hparams = hp
         self.step = 0
         self.device = torch.device(device)
-        g = torch.Generator().manual_seed(seed)
-        init = torch.rand(rows, dim, generator=g) / dim ** 0.5
-        self.master = init.to(self.device)
+        self.master = self._init_rows(rows, dim, seed).to(self.device)
         self.shadow = self.master.to(torch.bfloat16)
         names = self._STATE[optimizer]
         if optimizer == "sgd" and hp["momentum"]:
@@ -124,6 +149,30 @@ class EmbeddingTable(object):
         self.fused = bool(fused_apply or optimizer != "sgd"
                           or hp["momentum"] or hp["weight_decay"])
         self.lock = threading.Lock()
+
+    @staticmethod
+    def _init_rows(rows, dim, seed):
+        """The initial master (host fp32 [rows, dim]) of a table."""
+        g = torch.Generator().manual_seed(seed)
+        return torch.rand(rows, dim, generator=g) / dim ** 0.5
+
+    @classmethod
+    def shard_of(cls, name, rows, dim, shard, num_shards, strategy="mod",
+                 _full_init=None, **kw):
+        """Shard ``shard`` of the ``rows``-row table ``name`` split by row
+        over ``num_shards`` (``ops.shard_rows`` rows). Its initial master
+        is exactly the rows ``ops.shard_global_ids(...)`` of what
+        ``EmbeddingTable(name, rows, dim, **kw)`` draws: the FULL init is
+        generated on the host and the shard's rows are selected from it
+        (the generator's stream is sequential; a table too large for host
+        memory needs a per-row seeding scheme instead)."""
+        gids = ops.shard_global_ids(rows, num_shards, shard, strategy)
+        t = cls(name, len(gids), dim, **kw)
+        full = _full_init if _full_init is not None else \
+            cls._init_rows(rows, dim, kw.get("seed", 0))
+        t.master.copy_(full[gids.start:gids.stop:gids.step])
+        t.shadow.copy_(t.master.to(torch.bfloat16))
+        return t
 
     def pull(self, ids):
         """bf16 rows for ids (HIP gather on GPU)."""
@@ -166,13 +215,17 @@ class EmbeddingTable(object):
                             eps=hp["eps"], weight_decay=hp["weight_decay"],
                             bf16_out=self.shadow, **bag)
 
-    def pull_pooled(self, ids, offsets, weights=None, combiner="sum"):
+    def pull_pooled(self, ids, offsets, weights=None, combiner="sum",
+                    out_dtype=None):
         """bf16 [B,D] pooled rows from the shadow: bag b (positions
         [offsets[b], offsets[b+1]) of ids) summed or averaged, with
-        optional per-id weights (``ops.embedding_bag``)."""
+        optional per-id weights (``ops.embedding_bag``). out_dtype
+        torch.float32 returns the fp32 sums unrounded (the partials of a
+        row-sharded table)."""
         with self.lock:
             return ops.embedding_bag(self.shadow, ids, offsets,
-                                     weights=weights, combiner=combiner)
+                                     weights=weights, combiner=combiner,
+                                     out_dtype=out_dtype)
 
     def push_pooled(self, ids, offsets, bag_grads, weights=None,
                     combiner="sum", lr=None):
@@ -218,29 +271,277 @@ class EmbeddingTable(object):
             self.shadow.copy_(self.master.to(torch.bfloat16))
 
 
+class _ShardRoute(object):
+    """One request routed to the shards of a row-sharded table: THE routing
+    implementation, shared by ``ShardedEmbeddingTable`` (local shards) and
+    ``SparseWorkerClient`` (shards on PS ranks).
+
+    Partitions on the ids' device. ``starts`` is copied to the host once,
+    here: the per-shard counts size every message (and slice), so this is
+    the one unavoidable device->host sync of a sharded request. A "slot"
+    below is a position of the partitioned order; shard ``s`` owns slots
+    ``span(s)``."""
+
+    def __init__(self, ids, rows, num_shards, strategy):
+        self.n = ids.numel()
+        self.part = ops.shard_partition(ids, rows, num_shards, strategy)
+        self.bounds = self.part.starts.tolist()
+
+    def span(self, s):
+        return slice(self.bounds[s], self.bounds[s + 1])
+
+    def count(self, s):
+        return self.bounds[s + 1] - self.bounds[s]
+
+    def ids(self, s):
+        """Shard-local ids of shard s, in request order."""
+        return self.part.local[self.span(s)]
+
+    def to_slots(self, rows, dtype=None):
+        """Per-position rows [n,D] (or values [n]) in slot order, cast to
+        ``dtype`` in the same pass (``ops.permute_rows``)."""
+        if rows.shape[0] != self.n:
+            raise ValueError("need one row per id: %d ids, %d rows"
+                             % (self.n, rows.shape[0]))
+        if rows.dim() == 1:
+            return ops.permute_rows(rows.view(-1, 1), self.part.perm,
+                                    dtype).view(-1)
+        return ops.permute_rows(rows, self.part.perm, dtype)
+
+    def to_request_order(self, buf):
+        """The shards' answers, received into consecutive row slices of
+        ``buf`` [n,D], back in request order."""
+        return ops.embedding_gather(buf, self.part.inv)
+
+    def bags(self, offsets, weights, combiner):
+        """A bagged request per shard: (shard_offsets [S,B+1], weights in
+        slot order or None). The coefficients c_i are computed ONCE, here,
+        over the whole bags (W_b counts every position of the bag, whatever
+        its shard) and travel as weights; every shard then pools with
+        combiner "sum". An unweighted sum sends no weights."""
+        if combiner not in _COMBINERS:
+            raise ValueError("unknown combiner %r (have %s)"
+                             % (combiner, list(_COMBINERS)))
+        dev = self.part.perm.device
+        offsets = offsets.to(device=dev, dtype=torch.int64)
+        so = ops.shard_bag_offsets(self.part.perm, self.part.starts, offsets)
+        if weights is None and combiner == "sum":
+            return so, None
+        if weights is not None:
+            weights = weights.to(device=dev, dtype=torch.float32)
+        c = ops.bag_coefficients(self.n, offsets, weights, combiner)
+        return so, self.to_slots(c)
+
+
+def _sum_partials(parts, nbags, dim, device):
+    """Pooled pull of a sharded table: the shards' fp32 [B,D] partial sums
+    added in fp32 in shard order, rounded once to bf16."""
+    acc = torch.zeros(nbags, dim, device=device)
+    for p in parts:
+        acc += p
+    return acc.to(torch.bfloat16)
+
+
+class ShardedEmbeddingTable(object):
+    """A ``rows``-row table split by row over ``num_shards`` local
+    ``EmbeddingTable`` shards (``EmbeddingTable.shard_of``), in one
+    process: the reference semantics of a table sharded over PS ranks, and
+    a way to use the shards of several devices' worth of rows behind the
+    interface of one table. Requests are routed by ``_ShardRoute`` exactly
+    as ``SparseWorkerClient`` routes them.
+
+    After any sequence of pushes master, optimizer state and ``step`` of
+    the shards equal the unsharded ``EmbeddingTable(name, rows, dim,
+    **kw)``'s (``to_dense()``); row pulls are equal too. A pooled pull adds
+    one fp32 partial per shard in shard order and rounds once to bf16: it
+    equals the unsharded pull exactly when a bag's ids all sit in one
+    shard, and otherwise up to the order of the fp32 sum."""
+
+    def __init__(self, name, rows, dim, num_shards, strategy="mod",
+                 device="cpu", **kw):
+        ops.shard_rows(rows, num_shards, 0, strategy)   # validates
+        self.name = name
+        self.rows = rows
+        self.dim = dim
+        self.num_shards = num_shards
+        self.strategy = strategy
+        self.device = torch.device(device)
+        full = EmbeddingTable._init_rows(rows, dim, kw.get("seed", 0))
+        self.shards = [
+            EmbeddingTable.shard_of(name, rows, dim, s, num_shards, strategy,
+                                    _full_init=full, device=device, **kw)
+            for s in range(num_shards)]
+        self.optimizer = self.shards[0].optimizer
+
+    @property
+    def step(self):
+        steps = set(t.step for t in self.shards)
+        if len(steps) != 1:
+            raise RuntimeError("shards of %r disagree on step: %s"
+                               % (self.name, sorted(steps)))
+        return steps.pop()
+
+    def _route(self, ids):
+        return _ShardRoute(ids.to(self.device), self.rows, self.num_shards,
+                           self.strategy)
+
+    def pull(self, ids):
+        """bf16 rows for ids, in request order."""
+        r = self._route(ids)
+        buf = torch.empty(r.n, self.dim, dtype=torch.bfloat16,
+                          device=self.device)
+        for s, t in enumerate(self.shards):
+            if r.count(s):      # pulls skip empty shards
+                buf[r.span(s)] = t.pull(r.ids(s))
+        return r.to_request_order(buf)
+
+    def push(self, ids, grads, lr=None):
+        """Row push: EVERY shard gets a push, also one that receives no
+        ids, so that ``step`` stays in lockstep with an unsharded table."""
+        r = self._route(ids)
+        g = r.to_slots(grads.to(self.device))
+        for s, t in enumerate(self.shards):
+            t.push(r.ids(s), g[r.span(s)], lr)
+
+    def pull_pooled(self, ids, offsets, weights=None, combiner="sum"):
+        r = self._route(ids)
+        so, w = r.bags(offsets, weights, combiner)
+        parts = [t.pull_pooled(r.ids(s), so[s],
+                               None if w is None else w[r.span(s)], "sum",
+                               out_dtype=torch.float32)
+                 for s, t in enumerate(self.shards) if r.count(s)]
+        return _sum_partials(parts, so.shape[1] - 1, self.dim, self.device)
+
+    def push_pooled(self, ids, offsets, bag_grads, weights=None,
+                    combiner="sum", lr=None):
+        """Pooled push: every shard gets the [B,D] bag gradients."""
+        r = self._route(ids)
+        so, w = r.bags(offsets, weights, combiner)
+        bag_grads = bag_grads.to(self.device)
+        for s, t in enumerate(self.shards):
+            t.push_pooled(r.ids(s), so[s], bag_grads,
+                          None if w is None else w[r.span(s)], "sum", lr)
+
+    def _global_ids(self, s):
+        g = ops.shard_global_ids(self.rows, self.num_shards, s, self.strategy)
+        return torch.arange(g.start, g.stop, g.step, device=self.device)
+
+    def to_dense(self):
+        """Master, shadow, optimizer state (on ``device``, global row
+        order) and step, reassembled from the shards."""
+        def gather(pick, dtype=torch.float32):
+            out = torch.empty(self.rows, self.dim, dtype=dtype,
+                              device=self.device)
+            for s, t in enumerate(self.shards):
+                out[self._global_ids(s)] = pick(t)
+            return out
+        return {
+            "optimizer": self.optimizer,
+            "master": gather(lambda t: t.master),
+            "shadow": gather(lambda t: t.shadow, torch.bfloat16),
+            "state": {k: gather(lambda t: t.state[k])
+                      for k in self.shards[0].state},
+            "step": self.step,
+        }
+
+    def state_dict(self):
+        return {"optimizer": self.optimizer, "rows": self.rows,
+                "num_shards": self.num_shards, "strategy": self.strategy,
+                "shards": [t.state_dict() for t in self.shards]}
+
+    def load_state_dict(self, sd):
+        for k in ("rows", "num_shards", "strategy"):
+            if sd[k] != getattr(self, k):
+                raise ValueError("checkpoint has %s = %r, table has %r"
+                                 % (k, sd[k], getattr(self, k)))
+        for t, shard_sd in zip(self.shards, sd["shards"]):
+            t.load_state_dict(shard_sd)
+
+
 def make_sparse_pair_groups(ps_ranks, worker_ranks):
     """One Chan per (ps, worker) pair; collective — all ranks call."""
     return make_pair_chans(ps_ranks, worker_ranks)
+
+
+class _Posted(object):
+    """Non-blocking sends and receives posted on several channels and
+    awaited together (the pattern of ``pull_many``)."""
+
+    def __init__(self):
+        self.sends, self.keep, self.recvs = [], [], []
+
+    def send(self, c, t):
+        w, staged = c.isend(t)
+        self.sends.append(w)
+        self.keep.append(staged)    # alive until the work completes
+
+    def recv(self, c, t):
+        """Receive into ``t`` (a contiguous tensor or row slice); under
+        gloo a device tensor is received through a host buffer."""
+        buf = t if c.device_only or t.device.type == "cpu" else \
+            torch.empty(t.shape, dtype=t.dtype, device="cpu")
+        self.recvs.append((dist.irecv(buf, src=c.peer, group=c.group),
+                           buf, t))
+
+    def wait(self):
+        for w in self.sends:
+            w.wait()
+        for w, buf, t in self.recvs:
+            w.wait()
+            if buf is not t:
+                t.copy_(buf)
 
 
 class SparseWorkerClient(object):
     """Worker-side pull/push to the PS rank owning each table.
 
     All payloads stay on ``device`` end to end under RCCL (ids, rows
-    and grads ride xGMI); gloo stages via the Chan."""
+    and grads ride xGMI); gloo stages via the Chan. A table whose home is
+    a list of PS ranks is row-sharded over them: pull, push, pull_pooled
+    and push_pooled route each request to the shards (``pull_many`` /
+    ``push_many`` take unsharded tables only)."""
 
-    def __init__(self, rank, table_homes, dims, pair_chans, device="cpu"):
-        """table_homes: {table_name: ps_rank}; dims: {name: row_dim}."""
+    def __init__(self, rank, table_homes, dims, pair_chans, device="cpu",
+                 rows=None, strategy="mod"):
+        """table_homes: {table_name: ps_rank}, or for a row-sharded table
+        {table_name: [ps_rank of shard 0, of shard 1, ...]} (distinct
+        ranks); dims: {name: row_dim}. rows: {name: V}, the global row
+        count of every sharded table; strategy: "mod" or "div" for all
+        sharded tables, or {name: strategy}."""
         self.rank = rank
         self.homes = table_homes
         self.dims = dims
         self.chans = pair_chans
         self.device = torch.device(device)
+        self.rows = dict(rows or {})
+        self.strategy = strategy
+        for name, h in table_homes.items():
+            if not isinstance(h, (list, tuple)):
+                continue
+            if len(set(h)) != len(h):
+                raise ValueError("table %r: shard homes must be distinct PS "
+                                 "ranks, got %s" % (name, list(h)))
+            if name not in self.rows:
+                raise ValueError("sharded table %r needs rows={%r: V}"
+                                 % (name, name))
+            ops.shard_rows(self.rows[name], len(h), 0,
+                           self._strategy(name))    # validates
         import torch.distributed as dist
         self._hdr_dev = self.device if dist.get_backend() == "nccl" \
             else torch.device("cpu")
 
+    def _strategy(self, name):
+        if isinstance(self.strategy, dict):
+            return self.strategy.get(name, "mod")
+        return self.strategy
+
+    def _sharded(self, name):
+        return isinstance(self.homes[name], (list, tuple))
+
     def _chan(self, name):
+        if self._sharded(name):
+            raise ValueError("table %r is row-sharded: use pull / push / "
+                             "pull_pooled / push_pooled" % name)
         return self.chans[(self.homes[name], self.rank)]
 
     def _hdr(self, count, tidx):
@@ -248,6 +549,8 @@ class SparseWorkerClient(object):
                             device=self._hdr_dev)
 
     def pull(self, name, ids):
+        if self._sharded(name):
+            return self._pull_sharded(name, ids)
         c = self._chan(name)
         ids = ids.to(self.device)
         c.send(self._hdr(ids.numel(), self._tidx(name)))
@@ -258,20 +561,31 @@ class SparseWorkerClient(object):
         return rows
 
     def push(self, name, ids, grads):
+        if self._sharded(name):
+            return self._push_sharded(name, ids, grads)
         c = self._chan(name)
         ids = ids.to(self.device)
         c.send(self._hdr(-ids.numel(), self._tidx(name)))  # count<0 => push
         c.send(ids)
         c.send(grads.to(device=self.device, dtype=torch.bfloat16))
 
-    def _tidx(self, name):
-        mine = sorted(n for n, h in self.homes.items()
-                      if h == self.homes[name])
+    @staticmethod
+    def _on(home, ps):
+        return ps in home if isinstance(home, (list, tuple)) else ps == home
+
+    def _tidx(self, name, ps=None):
+        """Index of ``name`` among the tables PS rank ``ps`` holds (the
+        home of an unsharded table): the server sorts its tables by name,
+        and a shard carries its table's name."""
+        ps = self.homes[name] if ps is None else ps
+        mine = sorted(n for n, h in self.homes.items() if self._on(h, ps))
         return mine.index(name)
 
-    def _send_pooled(self, c, name, sign, ids, offsets, weights, combiner):
-        """Headers and index tensors of a pooled request (see
-        ``_pooled_hdr``). Returns B."""
+    def _pooled_msgs(self, tidx, sign, ids, offsets, weights, combiner,
+                     out_f32=False):
+        """Headers and index tensors of a pooled request, in wire order
+        (see the wire format at the top of this module). out_f32: ask for
+        the fp32 sums (a sharded table's partials)."""
         if combiner not in _COMBINERS:
             raise ValueError("unknown combiner %r (have %s)"
                              % (combiner, list(_COMBINERS)))
@@ -280,26 +594,35 @@ class SparseWorkerClient(object):
             raise ValueError("weights must be [n] = [%d]" % ids.numel())
         nbags = offsets.numel() - 1
         flags = _COMBINERS.index(combiner) | \
-            (_HAS_WEIGHTS if weights is not None else 0)
-        c.send(self._hdr(sign * (ids.numel() + 1),
-                         self._tidx(name) | _KIND_POOLED << _KIND_SHIFT))
-        c.send(self._hdr(nbags, flags))
+            (_HAS_WEIGHTS if weights is not None else 0) | \
+            (_OUT_F32 if out_f32 else 0)
+        msgs = [self._hdr(sign * (ids.numel() + 1),
+                          tidx | _KIND_POOLED << _KIND_SHIFT),
+                self._hdr(nbags, flags)]
         if ids.numel():     # no zero-size messages: the server skips them too
-            c.send(ids)
-        c.send(offsets.to(device=self.device, dtype=torch.int64))
+            msgs.append(ids)
+        msgs.append(offsets.to(device=self.device, dtype=torch.int64))
         if weights is not None and ids.numel():
-            c.send(weights.to(device=self.device, dtype=torch.float32))
-        return nbags
+            msgs.append(weights.to(device=self.device, dtype=torch.float32))
+        return msgs
+
+    def _send_pooled(self, c, name, sign, ids, offsets, weights, combiner):
+        for t in self._pooled_msgs(self._tidx(name), sign, ids, offsets,
+                                   weights, combiner):
+            c.send(t)
 
     def pull_pooled(self, name, ids, offsets, weights=None, combiner="sum"):
         """bf16 [B,D] pooled rows: the PS gathers and reduces each bag
         (``EmbeddingTable.pull_pooled``), so the link carries B x D bf16
         instead of n x D."""
-        c = self._chan(name)
         rows = torch.empty(offsets.numel() - 1, self.dims[name],
                            dtype=torch.bfloat16, device=self.device)
         if rows.shape[0] == 0:      # no bags: nothing to ask for
             return rows
+        if self._sharded(name):
+            return self._pull_pooled_sharded(name, ids, offsets, weights,
+                                             combiner)
+        c = self._chan(name)
         self._send_pooled(c, name, 1, ids, offsets, weights, combiner)
         c.recv_into(rows)
         return rows
@@ -308,14 +631,90 @@ class SparseWorkerClient(object):
                     combiner="sum"):
         """Push [B,D] bag gradients (sent as bf16); the PS applies
         c_i * bag_grads[b] per position (``EmbeddingTable.push_pooled``)."""
-        c = self._chan(name)
         if bag_grads.dim() != 2 or bag_grads.shape[0] != offsets.numel() - 1:
             raise ValueError("bag_grads must be [B,D] = [%d,D], got %s"
                              % (offsets.numel() - 1, tuple(bag_grads.shape)))
         if bag_grads.numel() == 0:      # no bags: nothing to push
             return
+        if self._sharded(name):
+            return self._push_pooled_sharded(name, ids, offsets, bag_grads,
+                                             weights, combiner)
+        c = self._chan(name)
         self._send_pooled(c, name, -1, ids, offsets, weights, combiner)
         c.send(bag_grads.to(device=self.device, dtype=torch.bfloat16))
+
+    # Row-sharded tables: every call partitions on the worker's device
+    # (_ShardRoute: one starts -> host copy, the request's only sync) and
+    # posts ALL shards' sends and receives before waiting on any.
+
+    def _route(self, name, ids):
+        return _ShardRoute(ids.to(self.device), self.rows[name],
+                           len(self.homes[name]), self._strategy(name))
+
+    def _shard_chans(self, name):
+        """[(shard, chan, table index on that PS)]."""
+        return [(s, self.chans[(p, self.rank)], self._tidx(name, p))
+                for s, p in enumerate(self.homes[name])]
+
+    def _pull_sharded(self, name, ids):
+        r = self._route(name, ids)
+        buf = torch.empty(r.n, self.dims[name], dtype=torch.bfloat16,
+                          device=self.device)
+        post = _Posted()
+        for s, c, tidx in self._shard_chans(name):
+            if not r.count(s):      # pulls skip empty shards
+                continue
+            post.send(c, self._hdr(r.count(s) + 1,
+                                   tidx | _KIND_ROWS << _KIND_SHIFT))
+            post.send(c, r.ids(s))
+            post.recv(c, buf[r.span(s)])
+        post.wait()
+        return r.to_request_order(buf)
+
+    def _push_sharded(self, name, ids, grads):
+        r = self._route(name, ids)
+        g = r.to_slots(grads.to(self.device), torch.bfloat16)
+        post = _Posted()
+        for s, c, tidx in self._shard_chans(name):
+            # every shard, also an empty one: its step must advance
+            post.send(c, self._hdr(-(r.count(s) + 1),
+                                   tidx | _KIND_ROWS << _KIND_SHIFT))
+            if r.count(s):
+                post.send(c, r.ids(s))
+                post.send(c, g[r.span(s)])
+        post.wait()
+
+    def _shard_bag_msgs(self, r, so, w, s, tidx, sign):
+        return self._pooled_msgs(tidx, sign, r.ids(s), so[s],
+                                 None if w is None else w[r.span(s)], "sum",
+                                 out_f32=sign > 0)
+
+    def _pull_pooled_sharded(self, name, ids, offsets, weights, combiner):
+        r = self._route(name, ids)
+        so, w = r.bags(offsets, weights, combiner)
+        nbags, dim = offsets.numel() - 1, self.dims[name]
+        post, parts = _Posted(), []
+        for s, c, tidx in self._shard_chans(name):
+            if not r.count(s):      # an empty shard's partial is zero
+                continue
+            for t in self._shard_bag_msgs(r, so, w, s, tidx, 1):
+                post.send(c, t)
+            parts.append(torch.empty(nbags, dim, device=self.device))
+            post.recv(c, parts[-1])
+        post.wait()
+        return _sum_partials(parts, nbags, dim, self.device)
+
+    def _push_pooled_sharded(self, name, ids, offsets, bag_grads, weights,
+                             combiner):
+        r = self._route(name, ids)
+        so, w = r.bags(offsets, weights, combiner)
+        g = bag_grads.to(device=self.device, dtype=torch.bfloat16)
+        post = _Posted()
+        for s, c, tidx in self._shard_chans(name):
+            for t in self._shard_bag_msgs(r, so, w, s, tidx, -1):
+                post.send(c, t)
+            post.send(c, g)
+        post.wait()
 
     def pull_many(self, reqs):
         """Concurrent pulls from multiple PS ranks: issue every
@@ -374,15 +773,20 @@ class SparseWorkerClient(object):
     def done_all(self):
         """One shutdown marker per PS RANK (its serving loop drops this
         worker's channel on the first zero-count header)."""
-        for p in sorted(set(self.homes.values())):
+        ranks = set()
+        for h in self.homes.values():
+            ranks.update(h if isinstance(h, (list, tuple)) else [h])
+        for p in sorted(ranks):
             self.chans[(p, self.rank)].send(self._hdr(0, 0))
 
 
 class SparsePSServer(object):
     """PS-side server, fixed request protocol (n>0: pull n ids; n<0:
     push |n| id/grad rows; n==0: worker done; pooled pulls and pushes
-    carry kind 1 in the header's second word — see the wire format at the
-    top of this module). Exits when every worker has sent done.
+    carry kind 1 in the header's second word, the row requests of sharded
+    tables kind 2 — see the wire format at the top of this module). A
+    shard of a row-sharded table is served like any other table. Exits
+    when every worker has sent done.
 
     Serving strategy by backend (same rationale as AsyncPSServer):
     nccl/RCCL = ONE polling loop over irecv'd headers (CUDA-event
@@ -408,6 +812,9 @@ class SparsePSServer(object):
         if word >> _KIND_SHIFT == _KIND_POOLED:
             self._handle_pooled(c, hdr, table, count)
             return True
+        if word >> _KIND_SHIFT == _KIND_ROWS:
+            self._handle_rows(c, table, count)
+            return True
         ids = c.recv_new((abs(count),), torch.int64, table.device)
         if count > 0:
             c.send(table.pull(ids))
@@ -416,6 +823,20 @@ class SparsePSServer(object):
                                table.device)
             table.push(ids, grads)
         return True
+
+    def _handle_rows(self, c, table, count):
+        """One kind-2 row request (count = +-(n + 1)): a push of zero rows
+        still reaches ``table.push``, which advances ``step``."""
+        n, dev = abs(count) - 1, table.device
+        ids = c.recv_new((n,), torch.int64, dev) if n else \
+            torch.empty(0, dtype=torch.int64, device=dev)
+        if count > 0:
+            if n:       # no zero-size messages
+                c.send(table.pull(ids))
+            return
+        grads = c.recv_new((n, table.dim), torch.bfloat16, dev) if n else \
+            torch.empty(0, table.dim, dtype=torch.bfloat16, device=dev)
+        table.push(ids, grads)
 
     def _handle_pooled(self, c, hdr, table, count):
         """One pooled request (count = +-(n + 1)); the second header is
@@ -432,7 +853,9 @@ class SparsePSServer(object):
             weights = c.recv_new((n,), torch.float32, dev) if n else \
                 torch.empty(0, device=dev)
         if count > 0:
-            c.send(table.pull_pooled(ids, offsets, weights, combiner))
+            c.send(table.pull_pooled(
+                ids, offsets, weights, combiner,
+                out_dtype=torch.float32 if flags & _OUT_F32 else None))
         else:
             grads = c.recv_new((nbags, table.dim), torch.bfloat16, dev)
             table.push_pooled(ids, offsets, grads, weights, combiner)
