@@ -17,7 +17,8 @@ pooled (bag) lookups: embedding_bag forward (TF's embedding_lookup_sparse,
 combiner sum / mean, optional weights) and the same sparse applies fed
 bag gradients (``offsets=``); and the routing of requests to a row-sharded
 table (TF's partitioned variable): shard_partition, permute_rows,
-shard_bag_offsets, bag_coefficients.
+shard_bag_offsets, bag_coefficients; and the worker-side coalescing of a row
+request (TF's unique / unsorted_segment_sum): coalesce_ids, segment_sum_rows.
 """
 
 import collections
@@ -561,6 +562,85 @@ def bag_coefficients(n, offsets, weights=None, combiner="sum"):
             int(n), offsets.contiguous(),
             _bag_weights(weights, offsets.device), combiner == "mean")
     return _bag_expand_cpu(torch.empty(n), offsets, weights, combiner)[1]
+
+
+# ------------------------------------------------ coalescing a row request
+#
+# What TF's PS does before a row request reaches the wire: embedding_lookup
+# gathers each DISTINCT id once (unique), and a sparse gradient has its
+# duplicate indices summed (unsorted_segment_sum). coalesce_ids finds the
+# distinct ids of a request, segment_sum_rows sums the gradient rows per
+# distinct id in fp32 and rounds once. GPU: csrc/coalesce.hip — no atomics,
+# bit-reproducible, nothing read back.
+
+Coalesced = collections.namedtuple(
+    "Coalesced", ["uniq", "inverse", "perm", "seg", "count"])
+Coalesced.__doc__ = """The distinct ids of a request's ids [n], all int64 on
+the ids' device. With u distinct ids:
+
+uniq [n]: the distinct ids ascending in uniq[:u], -1 behind them;
+inverse [n]: uniq[inverse[i]] == ids[i]; perm [n]: the permutation of the
+stable sort of ids (positions grouped by id, request order inside a group);
+seg [n+1]: seg[k] is the first sorted position of distinct id k for k < u
+and n for k >= u; count [1]: u."""
+
+
+@torch.no_grad()
+def coalesce_ids(ids):
+    """The distinct ids of ids int64 [n] (n < 2**31) -> Coalesced. The ids'
+    range does not matter: negative and too-large ids are distinct values
+    like any other. GPU: stable torch.sort, then head flags / count / scan
+    / scatter (csrc/coalesce.hip; the scan is torch.cumsum), no host sync.
+    CPU: torch.unique and a stable sort."""
+    if ids.dim() != 1 or ids.dtype != torch.int64:
+        raise ValueError("ids must be int64 [n]")
+    n = ids.numel()
+    if n >= 2 ** 31:
+        raise ValueError("coalesce_ids: n must be below 2**31")
+    if ids.is_cuda:
+        return Coalesced(*_ext().coalesce_ids(ids.contiguous()))
+    u, inverse = torch.unique(ids, sorted=True, return_inverse=True)
+    perm = torch.sort(ids, stable=True)[1]
+    uniq = torch.full((n,), -1, dtype=torch.int64)
+    uniq[:u.numel()] = u
+    seg = torch.full((n + 1,), n, dtype=torch.int64)
+    lens = torch.bincount(inverse, minlength=u.numel())
+    seg[:u.numel()] = lens.cumsum(0) - lens
+    return Coalesced(uniq, inverse, perm, seg, torch.tensor([u.numel()]))
+
+
+@torch.no_grad()
+def segment_sum_rows(rows, perm, seg, num, out_dtype=None):
+    """out [num,D]: out[k] = sum of rows[perm[j]] over j in
+    [seg[k], seg[k+1]) — fp32 accumulation in that order, rounded ONCE to
+    out_dtype (default: rows' dtype). rows [n,D] fp32 or bf16, out fp32 or
+    bf16; perm / seg as coalesce_ids returns them, num (a host int) <= the
+    number of distinct ids. GPU: one wave per output row, runs longer than
+    512 cut into pieces summed by separate waves (csrc/coalesce.hip)."""
+    out_dtype = rows.dtype if out_dtype is None else out_dtype
+    ok = (torch.float32, torch.bfloat16)
+    if rows.dim() != 2 or rows.dtype not in ok or out_dtype not in ok:
+        raise ValueError("segment_sum_rows: rows must be [n,D] fp32 or bf16 "
+                         "and out_dtype fp32 or bf16")
+    n = rows.shape[0]
+    if perm.dim() != 1 or perm.numel() != n:
+        raise ValueError("segment_sum_rows: need one perm entry per row: "
+                         "%d rows, perm %s" % (n, tuple(perm.shape)))
+    num = int(num)
+    if num < 0 or seg.dim() != 1 or seg.numel() < num + 1:
+        raise ValueError("segment_sum_rows: seg must hold num + 1 = %d "
+                         "entries, got %s" % (num + 1, tuple(seg.shape)))
+    if rows.is_cuda:
+        return _ext().segment_sum_rows(rows.contiguous(), perm.contiguous(),
+                                       seg.contiguous(), num,
+                                       out_dtype == torch.bfloat16)
+    # the segment of every sorted position: the ends seg[1:num+1] at or
+    # before it; positions behind seg[num] belong to no output row
+    of = torch.bucketize(torch.arange(n), seg[1:num + 1], right=True)
+    keep = of < num
+    out = torch.zeros(num, rows.shape[1])
+    out.index_add_(0, of[keep], rows.float().index_select(0, perm[keep]))
+    return out.to(out_dtype)
 
 
 # ------------------------------------------------- sparse optimizer applies

@@ -69,6 +69,14 @@ void launch_shard_bag_offsets(const long*, const long*, const long*, long*,
                               long, long, int, hipStream_t);
 void launch_bag_coef(const long*, const float*, float*, long, long, bool,
                      hipStream_t);
+long coalesce_windows(long);
+void launch_coalesce_count(const long*, int*, long, hipStream_t);
+void launch_coalesce_scatter(const long*, const long*, const long*, long*,
+                             long*, long*, long*, long, hipStream_t);
+long segment_scratch_rows(long);
+void launch_segment_sum_rows(const void*, bool, const long*, const long*,
+                             float*, void*, bool, long, long, int,
+                             hipStream_t);
 void launch_relu_bwd(const bf16_t*, const bf16_t*, bf16_t*, long,
                      hipStream_t);
 void launch_add_n(const bf16_t* const*, int, bf16_t*, long, hipStream_t);
@@ -1055,6 +1063,82 @@ torch::Tensor bag_coefficients(long n, torch::Tensor offsets,
   return coef;
 }
 
+// The distinct ids of a request (coalesce.hip): stable sort of the ids and
+// cumsum of the per-window head counts are plumbing (they stay on the
+// device), the count and scatter kernels are ours. Returns uniq, inverse,
+// perm [n], seg [n+1] and count [1]; no host sync.
+std::vector<torch::Tensor> coalesce_ids(torch::Tensor ids) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == torch::kInt64 &&
+              ids.dim() == 1 && ids.is_contiguous(),
+              "coalesce_ids: ids must be contiguous i64 [n] on GPU");
+  const long n = ids.numel();
+  TORCH_CHECK(n < (long)INT_MAX, "coalesce_ids: n must be below 2^31");
+  auto opt = ids.options();
+  if (n == 0)   // a zero-size grid is a launch error
+    return {torch::empty({0}, opt), torch::empty({0}, opt),
+            torch::empty({0}, opt), torch::zeros({1}, opt),
+            torch::zeros({1}, opt)};
+  auto st = torch::sort(ids, /*stable=*/true, /*dim=*/0,
+                        /*descending=*/false);
+  const torch::Tensor sorted = std::get<0>(st), perm = std::get<1>(st);
+  auto uniq = torch::empty({n}, opt), inverse = torch::empty({n}, opt);
+  auto seg = torch::empty({n + 1}, opt), count = torch::empty({1}, opt);
+  auto counts = torch::empty({coalesce_windows(n)}, opt.dtype(torch::kInt32));
+  launch_coalesce_count(sorted.data_ptr<long>(), counts.data_ptr<int>(), n,
+                        cur_stream());
+  auto incl = torch::cumsum(counts, 0, torch::kInt64);
+  launch_coalesce_scatter(sorted.data_ptr<long>(), perm.data_ptr<long>(),
+                          incl.data_ptr<long>(), uniq.data_ptr<long>(),
+                          inverse.data_ptr<long>(), seg.data_ptr<long>(),
+                          count.data_ptr<long>(), n, cur_stream());
+  return {uniq, inverse, perm, seg, count};
+}
+
+// out[k] = sum of rows[perm[j]] over j in [seg[k], seg[k+1]), k < num: fp32
+// accumulation in that order, rounded once (coalesce.hip). The contents of
+// perm and seg are a caller contract (not read back); the kernels clamp
+// what they derive from them.
+torch::Tensor segment_sum_rows(torch::Tensor rows, torch::Tensor perm,
+                               torch::Tensor seg, long num, bool out_bf16) {
+  TORCH_CHECK(rows.is_cuda() && rows.dim() == 2 && rows.is_contiguous(),
+              "segment_sum_rows: rows must be contiguous [n,D] on GPU");
+  const bool r_bf16 = rows.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(r_bf16 || rows.scalar_type() == torch::kFloat32,
+              "segment_sum_rows: rows must be bf16 or fp32");
+  auto ok = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.scalar_type() == torch::kInt64 && t.dim() == 1 &&
+           t.is_contiguous();
+  };
+  TORCH_CHECK(ok(perm) && ok(seg), "segment_sum_rows: perm and seg must be "
+              "contiguous i64 vectors on GPU");
+  const long n = rows.size(0), D = rows.size(1);
+  TORCH_CHECK(perm.numel() == n, "segment_sum_rows: perm must be [n]");
+  TORCH_CHECK(num >= 0 && seg.numel() >= num + 1,
+              "segment_sum_rows: seg must hold num + 1 entries");
+  const long tiles = (D + 255) / 256;
+  TORCH_CHECK(n < (long)INT_MAX && D <= (long)INT_MAX &&
+              num * tiles / 4 < (long)INT_MAX &&
+              (n / 256 + 1) * tiles / 4 < (long)INT_MAX,
+              "segment_sum_rows: too large for one grid");
+  auto out = torch::empty({num, D},
+                          rows.options().dtype(out_bf16 ? torch::kBFloat16
+                                                        : torch::kFloat32));
+  if (num == 0 || D == 0) return out;   // a zero-size grid is a launch error
+  if (n == 0) return out.zero_();
+  torch::Tensor scratch;
+  float* scratch_p = nullptr;
+  const long srows = segment_scratch_rows(n);
+  if (srows > 0) {
+    scratch = torch::empty({srows, D},
+                           rows.options().dtype(torch::kFloat32));
+    scratch_p = scratch.data_ptr<float>();
+  }
+  launch_segment_sum_rows(rows.data_ptr(), r_bf16, perm.data_ptr<long>(),
+                          seg.data_ptr<long>(), scratch_p, out.data_ptr(),
+                          out_bf16, n, num, (int)D, cur_stream());
+  return out;
+}
+
 torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor act) {
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16 &&
               dy.is_contiguous() && act.is_contiguous() &&
@@ -1695,6 +1779,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-position bag coefficients c [n]",
         py::arg("n"), py::arg("offsets"), py::arg("weights"),
         py::arg("mean"));
+  m.def("coalesce_ids", &coalesce_ids,
+        "distinct ids of a request: uniq, inverse, perm, seg, count",
+        py::arg("ids"));
+  m.def("segment_sum_rows", &segment_sum_rows,
+        "out[k] = sum of rows[perm[seg[k]:seg[k+1]]], rounded once",
+        py::arg("rows"), py::arg("perm"), py::arg("seg"), py::arg("num"),
+        py::arg("out_bf16"));
   m.def("relu_bwd", &relu_bwd);
   m.def("colsum", &colsum, py::arg("x"), py::arg("out"));
 }
