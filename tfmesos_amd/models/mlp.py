@@ -5,16 +5,21 @@ Same architecture/hyperparameters as the reference benchmark workload
 stddev 1/sqrt(784), hidden 100, batch 100, lr 0.01). Forward AND backward
 are written explicitly against ``tfmesos_amd.ops`` (bf16 MFMA GEMM +
 fused softmax-xent + fused relu-bwd on GPU) — no autograd in the hot
-path, so the step is a short fixed kernel sequence (5 kernels at the
-benchmark geometry; GraphedStep can capture it and self-tunes
-graph-vs-eager).
+path, so the step is a short fixed kernel sequence (3 kernels at the
+benchmark geometry: fwd split-K stripes, their reduce, and the fused
+head+tail; GraphedStep can capture it and self-tunes graph-vs-eager).
 """
 
 import math
+import os
 
 import torch
 
 from tfmesos_amd import ops
+
+# TFA_MLP_HEADTAIL=0 selects the previous head kernel + tail kernel
+# sequence (one more launch) for A/B comparison
+_HEADTAIL = os.environ.get("TFA_MLP_HEADTAIL", "1") != "0"
 
 
 class MnistMLP(object):
@@ -54,6 +59,12 @@ class MnistMLP(object):
             ("sm_b", torch.zeros(self.classes)),
         ]
 
+    def _headtail_ok(self, x, min_tiles=2):
+        """Shape limits of ops.mlp_head_tail_* beyond the head's own."""
+        tiles = ((x.shape[1] + 31) // 32) * ((self.hidden + 31) // 32)
+        return (_HEADTAIL and self.hidden % 4 == 0
+                and min_tiles <= tiles <= 512)
+
     def fwd_bwd(self, p, x, y, g):
         """One replica fwd+bwd.
 
@@ -68,8 +79,23 @@ class MnistMLP(object):
 
         # fwd hidden layer: split-K GEMM + bias + relu
         h = ops.gemm_bias_act(x, hid_w, hid_b, act="relu")       # [B,H]
-        if x.is_cuda and B <= 128 and self.hidden <= 128 \
-                and self.classes <= 16:
+        small = B <= 128 and self.hidden <= 128 and self.classes <= 16
+        # from 32 tiles up (where gemm_bias_act runs dW1 on the
+        # small-tile kernel); the op is exact below as well, but only
+        # this regime was measured faster, so smaller grids keep the
+        # two-kernel sequence
+        if small and self._headtail_ok(x, 32 if x.is_cuda else 2) and (
+                not x.is_cuda or g("hid_w").dtype == g("sm_w").dtype):
+            # head + dW1 tail in ONE kernel (csrc/gemm.hip
+            # mlp_head_tail_kernel): each block of the dW1 GEMM
+            # recomputes the logits/softmax/dh slice it consumes, so
+            # the head launch, dh and dlogits disappear — 3 launches
+            # (fwd GEMM stripes, its reduce, head+tail) + the apply
+            return ops.mlp_head_tail_grads(
+                x, h, sm_w, sm_b, y, g("hid_w"), g("hid_b"),
+                g("sm_w"), g("sm_b"))
+        if x.is_cuda and small:
+            # TFA_MLP_HEADTAIL=0, or a shape outside the fused kernel:
             # the whole classifier head in ONE MFMA kernel
             # (csrc/softmax_xent.hip): logits GEMM + softmax + loss +
             # dlogits + relu-masked dh + dW2/db2. At this size each
@@ -111,16 +137,31 @@ class MnistMLP(object):
                 and self.classes <= 16)
 
     def fwd_bwd_apply(self, trainer, x, y, lr):
-        """One fused replica step (world==1 fast path): fwd GEMM ->
-        head (loss, dh, classifier grads) -> ONE tail kernel that
-        computes dW1 and applies SGD to all four params in its
-        epilogue (ops.mlp_tail_sgd). 4 kernels/step vs 5 — the flat
-        sgd apply launch disappears; same math as fwd_bwd + step
-        (plain SGD, grad mean over the single worker = 1).
+        """One fused replica step (world==1 fast path): fwd GEMM
+        (stripes + reduce, which also snapshots the 2 KB classifier
+        shadow) -> ONE head+tail kernel that recomputes the
+        classifier head per wave, computes dW1 and applies SGD to all
+        four params (ops.mlp_head_tail_sgd). 3 kernels/step; same
+        math, bit for bit, as the previous head kernel + tail kernel
+        sequence (ops.mlp_head_fused -> ops.mlp_tail_sgd), which
+        TFA_MLP_HEADTAIL=0 or a shape outside the fused kernel's
+        limits selects (plain SGD, grad mean over the single worker
+        = 1).
         """
         st = trainer.store
         p = lambda n: st.view(n, bf16=True)
         g = trainer.grad_view
+        if self._headtail_ok(x):
+            # the fwd GEMM's stripe reduce snapshots W2/b2 on its way,
+            # so the fused kernel can apply them without a ticket
+            h, snap = ops.mlp_fwd_snap(x, p("hid_w"), p("hid_b"),
+                                       p("sm_w"), p("sm_b"))
+            loss = ops.mlp_head_tail_sgd(
+                x, h, p("sm_w"), p("sm_b"), y, st.view("hid_w"),
+                st.view("hid_b"), st.view("sm_w"), st.view("sm_b"),
+                p("hid_w"), p("hid_b"), lr, snap=snap)
+            st.global_step += 1
+            return loss
         h = ops.gemm_bias_act(x, p("hid_w"), p("hid_b"), act="relu")
         loss, _, dh = ops.mlp_head_fused(
             h, p("sm_w"), p("sm_b"), y, dw2=g("sm_w"), db2=g("sm_b"))

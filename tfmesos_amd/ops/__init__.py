@@ -1273,6 +1273,70 @@ def mlp_tail_sgd(x, dh, w1_m, w1_s, b1_m, b1_s, g_w2, w2_m, w2_s,
                                float(lr))
 
 
+def mlp_head_tail_grads(x, h, w2, b2, y, dw1, db1, dw2, db2):
+    """Classifier head + dW1 tail in ONE kernel (GPU, csrc/gemm.hip
+    mlp_head_tail_kernel): every block of the dW1 = x^T @ dh GEMM
+    recomputes the logits / softmax / dh slice it consumes, so dh never
+    touches global memory; block (0,0) also produces dW2, db2 and the
+    loss. Fills dw1, db1, dw2, db2 (one dtype, fp32 or bf16) and returns
+    the mean loss — bit-identical to mlp_head_fused + gemm_bias_act's
+    dW1 GEMM (the small-tile kernel's sum order from 32 tiles up, the
+    64x64 kernel's below). Limits: B<=128, H<=128 (H%4==0), C<=16,
+    2..512 32x32 tiles. CPU: composed fp32 reference."""
+    if x.is_cuda:
+        return _ext().mlp_head_tail_grads(x, h, w2, b2, y, dw1, db1,
+                                          dw2, db2)
+    loss, _, dh = mlp_head_fused(h, w2, b2, y, dw2=dw2, db2=db2)
+    dhf = dh.float()
+    dw1.copy_((x.float().t() @ dhf).to(dw1.dtype))
+    db1.copy_(dhf.sum(0).to(db1.dtype))
+    return loss
+
+
+def mlp_fwd_snap(x, w1, b1, w2_s, b2_s):
+    """mnist fwd hidden layer h = relu(x @ w1 + b1) (same kernels and
+    bits as gemm_bias_act) whose split-K stripe reduce ALSO copies the
+    2 KB classifier shadow (w2_s, b2_s) into a per-device snapshot
+    buffer. Returns (h, snap) for mlp_head_tail_sgd(snap=...): reading
+    the snapshot instead of the live shadow lets it apply W2/b2 without
+    the arrival ticket (~5 us). snap is None where the GEMM runs a path
+    without that reduce kernel, and on CPU."""
+    if x.is_cuda:
+        h, snap = _ext().mlp_fwd_snap(x, w1, b1, w2_s, b2_s)
+        return h, (snap if snap.numel() else None)
+    return gemm_bias_act(x, w1, b1, act="relu"), None
+
+
+@torch.no_grad()
+def mlp_head_tail_sgd(x, h, w2_s, b2_s, y, w1_m, b1_m, w2_m, b2_m,
+                      w1_s, b1_s, lr, snap=None):
+    """mnist single-GPU step, head + tail + plain-SGD apply in ONE kernel
+    (GPU): as mlp_head_tail_grads, with W1/b1 applied straight from the
+    fp32 accumulators and W2/b2 (read from the live shadows w2_s/b2_s,
+    grads rounded to bf16 as the two-kernel path stores them) applied by
+    the block that arrives last — or, given mlp_fwd_snap's ``snap`` of
+    this step, by a fixed block concurrently (the kernel then reads
+    W2/b2 from the snapshot). *_m are the fp32 masters, *_s the bf16
+    shadows; all eight are updated in place. Returns the mean loss.
+    Only valid for sgd without momentum/weight-decay and grad_scale 1.
+    CPU: composed fp32 reference."""
+    if x.is_cuda:
+        return _ext().mlp_head_tail_sgd(
+            x, h, w2_s, b2_s, y, w1_m, b1_m, w2_m, b2_m, w1_s, b1_s,
+            float(lr), snap if snap is not None
+            else torch.empty(0, dtype=torch.bfloat16, device=x.device))
+    dw2 = torch.empty_like(w2_s)
+    db2 = torch.empty_like(b2_s)
+    loss, _, dh = mlp_head_fused(h, w2_s, b2_s, y, dw2=dw2, db2=db2)
+    dhf = dh.float()
+    grads = ((w1_m, w1_s, x.float().t() @ dhf), (b1_m, b1_s, dhf.sum(0)),
+             (w2_m, w2_s, dw2.float()), (b2_m, b2_s, db2.float()))
+    for m, s, g in grads:
+        m.add_(g.reshape(m.shape), alpha=-float(lr))
+        s.copy_(m.to(s.dtype))
+    return loss
+
+
 def mlp_fwd_head_fused(x, w1, b1, w2, b2, labels, scale=None,
                        dw2=None, db2=None):
     """Whole MLP fwd + classifier head in TWO kernels (GPU): split-K

@@ -32,6 +32,30 @@ struct SmallSgdArgs {
   int n2w, n2b;
 };
 
+// optional side job of the small split-K stripe reduce (gemm.hip): copy
+// two small bf16 ranges into dst[0..n0) and dst[off1..off1+n1) — the
+// mnist step snapshots the classifier shadow there, one launch ahead
+// of the fused head+tail kernel that reads it
+struct SnapArgs {
+  const void* s0; const void* s1;
+  void* dst;
+  int n0, n1, off1;
+};
+
+// host-side descriptor for the fused head+tail kernel (gemm.hip)
+struct HeadTailArgs {
+  const void* h;              // [B,H] bf16 relu output
+  const void* w2;             // [H,C] bf16 (sgd mode: the live shadow)
+  const void* b2;             // [C] bf16
+  const long* labels;         // [B]
+  float* loss;
+  void* dw2; void* db2;       // grads mode outputs (grad dtype)
+  unsigned* ticket;           // sgd mode: zeroed 16B-aligned device word,
+                              // or null when w2/b2 are a snapshot
+  float scale;
+  int C;
+};
+
 #define HIP_CHECK(expr)                                                     \
   do {                                                                      \
     hipError_t _e = (expr);                                                 \

@@ -21,7 +21,7 @@ void launch_adagrad(float*, const void*, bool, float*, bf16_t*, long, float,
 void launch_gemm(const bf16_t*, const bf16_t*, const void*, bool, void*,
                  bool, const bf16_t*, void*, float*, int*, int, int, int,
                  int, int, int, int, int, bool, bool, int, int, int,
-                 hipStream_t);
+                 hipStream_t, const SnapArgs* = nullptr, bool* = nullptr);
 void launch_softmax_xent_fwd(const bf16_t*, const long*, bf16_t*, float*,
                              int, int, hipStream_t);
 void launch_softmax_xent_fused(const bf16_t*, const long*, bf16_t*, float*,
@@ -42,6 +42,9 @@ void launch_gemm_stripes(const bf16_t*, const bf16_t*, float*, int, int,
 void launch_gemm_small(const bf16_t*, const bf16_t*, const void*, bool,
                        void*, bool, int, void*, bool, int, int, int, int,
                        int, int, bool, const SmallSgdArgs*, hipStream_t);
+void launch_mlp_head_tail(const bf16_t*, const HeadTailArgs*, void*, void*,
+                          bool, int, int, int, const SmallSgdArgs*,
+                          hipStream_t);
 void launch_gemm_stripes_any(const bf16_t*, const bf16_t*, float*, int, int,
                              int, int, int, int, int, int, bool, bool, int,
                              int, hipStream_t);
@@ -225,10 +228,13 @@ float* splitk_ws(const torch::Device& dev, long n, long ntiles, int** cnt) {
   return w.data_ptr<float>();
 }
 
-torch::Tensor gemm_bias_act_out(torch::Tensor a, torch::Tensor b,
-                                torch::Tensor bias, long act, bool trans_a,
-                                bool trans_b, torch::Tensor out,
-                                torch::Tensor aux, torch::Tensor colsum_out) {
+// snap / snap_taken: optional side copy riding the small stripe reduce
+// (see SnapArgs); *snap_taken stays false on every other kernel path
+torch::Tensor gemm_bias_act_impl(torch::Tensor a, torch::Tensor b,
+                                 torch::Tensor bias, long act, bool trans_a,
+                                 bool trans_b, torch::Tensor out,
+                                 torch::Tensor aux, torch::Tensor colsum_out,
+                                 const SnapArgs* snap, bool* snap_taken) {
   TORCH_CHECK(a.is_cuda() && b.is_cuda(), "gemm: tensors must be on GPU");
   TORCH_CHECK(a.scalar_type() == torch::kBFloat16 &&
               b.scalar_type() == torch::kBFloat16, "gemm: bf16 inputs only");
@@ -347,8 +353,47 @@ torch::Tensor gemm_bias_act_out(torch::Tensor a, torch::Tensor b,
               ws, cnt, kc, nslice, M, N, Ka, a.size(1), b.size(1), N,
               trans_a, trans_b, (int)act,
               vec_level(a.data_ptr(), a.size(1)),
-              vec_level(b.data_ptr(), b.size(1)), cur_stream());
+              vec_level(b.data_ptr(), b.size(1)), cur_stream(), snap,
+              snap_taken);
   return out;
+}
+
+torch::Tensor gemm_bias_act_out(torch::Tensor a, torch::Tensor b,
+                                torch::Tensor bias, long act, bool trans_a,
+                                bool trans_b, torch::Tensor out,
+                                torch::Tensor aux, torch::Tensor colsum_out) {
+  return gemm_bias_act_impl(a, b, bias, act, trans_a, trans_b, out, aux,
+                            colsum_out, nullptr, nullptr);
+}
+
+// mnist fwd hidden layer h = relu(x @ w1 + b1) whose stripe reduce also
+// snapshots the classifier shadow (w2s [H,C], b2s [C]) for the fused
+// head+tail kernel that follows. Returns (h, snap): snap is the
+// per-device snapshot buffer (w2 at 0, b2 at 2048), or EMPTY when the
+// GEMM took a kernel path without the small stripe reduce — the caller
+// then uses the live shadow and the arrival ticket.
+constexpr int kSnapB2Off = 2048;
+std::vector<torch::Tensor> mlp_fwd_snap(torch::Tensor x, torch::Tensor w1,
+                                        torch::Tensor b1, torch::Tensor w2s,
+                                        torch::Tensor b2s) {
+  for (auto* t : {&w2s, &b2s})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->scalar_type() == torch::kBFloat16,
+                "w2s/b2s must be contiguous bf16 on GPU");
+  TORCH_CHECK(w2s.numel() <= kSnapB2Off && b2s.numel() <= 16,
+              "classifier too large for the snapshot buffer");
+  static std::unordered_map<int, torch::Tensor> smap;
+  auto& sb = smap[x.device().index()];
+  if (!sb.defined())
+    sb = torch::zeros({kSnapB2Off + 64}, w2s.options());
+  SnapArgs sa;
+  sa.s0 = w2s.data_ptr(); sa.s1 = b2s.data_ptr(); sa.dst = sb.data_ptr();
+  sa.n0 = (int)w2s.numel(); sa.n1 = (int)b2s.numel(); sa.off1 = kSnapB2Off;
+  bool taken = false;
+  auto empty = torch::empty({0}, x.options());
+  auto h = gemm_bias_act_impl(x, w1, b1, 1, false, false, empty, empty,
+                              empty, &sa, &taken);
+  return {h, taken ? sb : empty};
 }
 
 // GEMM -> SGD fusion for the NMF factor updates: the gradient
@@ -591,8 +636,12 @@ std::vector<torch::Tensor> mlp_head_fused(torch::Tensor h, torch::Tensor w,
   TORCH_CHECK(w.is_contiguous() && w.dim() == 2 && w.size(0) == h.size(1) &&
               w.scalar_type() == torch::kBFloat16, "w must be bf16 [H,C]");
   const int B = h.size(0), H = h.size(1), C = w.size(1);
+  // the B*(H+8) bound is the LDS staging of the one-thread-per-row
+  // kernel only; the MFMA path (B<=128, H<=128, H%4==0) has fixed
+  // 128-row tiles and takes its limits full
+  const bool mfma = B <= 128 && H <= 128 && (H & 3) == 0;
   TORCH_CHECK(C <= 16 && H <= 512 && B <= 512 &&
-              (long)B * (H + 8) <= 15000,
+              (mfma || (long)B * (H + 8) <= 15000),
               "mlp_head_fused limits: C<=16, H<=512, B<=512, "
               "B*(H+8)<=15000");
   TORCH_CHECK(b.scalar_type() == torch::kBFloat16 && b.numel() == C,
@@ -1700,6 +1749,148 @@ void mlp_tail_sgd(torch::Tensor x, torch::Tensor dh,
                     /*ta=*/true, &sga, cur_stream());
 }
 
+// Shared argument checks of the fused head+tail ops: the limits of the
+// two kernels it replaces (head: B<=128, H<=128, H%4==0, C<=16; tail:
+// 2..512 32x32 tiles), returned as a filled HeadTailArgs.
+static HeadTailArgs head_tail_args(const torch::Tensor& x,
+                                   const torch::Tensor& h,
+                                   const torch::Tensor& w2,
+                                   const torch::Tensor& b2,
+                                   const torch::Tensor& y,
+                                   torch::Tensor& loss) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
+              x.scalar_type() == torch::kBFloat16, "x must be bf16 [B,M]");
+  TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() &&
+              h.scalar_type() == torch::kBFloat16 &&
+              h.size(0) == x.size(0), "h must be bf16 [B,H]");
+  TORCH_CHECK(w2.is_cuda() && w2.dim() == 2 && w2.is_contiguous() &&
+              w2.scalar_type() == torch::kBFloat16 &&
+              w2.size(0) == h.size(1), "w2 must be bf16 [H,C]");
+  const long B = x.size(0), M = x.size(1), H = h.size(1), C = w2.size(1);
+  TORCH_CHECK(b2.is_cuda() && b2.is_contiguous() &&
+              b2.scalar_type() == torch::kBFloat16 && b2.numel() == C,
+              "b2 must be bf16 [C]");
+  TORCH_CHECK(y.is_cuda() && y.is_contiguous() &&
+              y.scalar_type() == torch::kInt64 && y.numel() == B,
+              "labels must be int64 [B]");
+  TORCH_CHECK(B >= 1 && B <= 128 && H <= 128 && (H & 3) == 0 && C >= 1 &&
+              C <= 16, "mlp_head_tail limits: B<=128, H<=128, H%4==0, "
+              "C<=16");
+  const long stiles = ((M + 31) / 32) * ((H + 31) / 32);
+  TORCH_CHECK(stiles >= 2 && stiles <= 512,
+              "shape outside the small-GEMM regime");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+              (uintptr_t)h.data_ptr() % 8 == 0,
+              "x must be 16-byte and h 8-byte aligned");
+  loss = torch::empty({}, h.options().dtype(torch::kFloat32));
+  HeadTailArgs a = {};
+  a.h = h.data_ptr();
+  a.w2 = w2.data_ptr();
+  a.b2 = b2.data_ptr();
+  a.labels = y.data_ptr<long>();
+  a.loss = loss.data_ptr<float>();
+  a.scale = 1.0f / (float)B;
+  a.C = (int)C;
+  return a;
+}
+
+// arrival ticket of the sgd-mode kernel: one zeroed device word per
+// device, allocated on the first (eager) call; the kernel leaves it 0
+static unsigned* head_tail_ticket(const torch::Device& dev) {
+  static std::unordered_map<int, torch::Tensor> tmap;
+  auto& tk = tmap[dev.index()];
+  if (!tk.defined())
+    tk = torch::zeros({4}, torch::dtype(torch::kInt32).device(dev));
+  return (unsigned*)tk.data_ptr<int>();
+}
+
+// mnist single-GPU step, launches 3+4 fused: the classifier head is
+// recomputed per wave inside the dW1 tail, and plain SGD is applied to
+// all four params (W1/b1 from the fp32 accumulators, W2/b2 by the block
+// that arrives last, from bf16-rounded grads). w2s/b2s are read AND
+// updated. snap (optional, else empty): mlp_fwd_snap's copy of w2s/b2s
+// taken by the preceding launch — read instead of the live shadow, so
+// a fixed block applies W2/b2 without the ticket. Returns the mean loss.
+torch::Tensor mlp_head_tail_sgd(torch::Tensor x, torch::Tensor h,
+                                torch::Tensor w2s, torch::Tensor b2s,
+                                torch::Tensor y,
+                                torch::Tensor w1m, torch::Tensor b1m,
+                                torch::Tensor w2m, torch::Tensor b2m,
+                                torch::Tensor w1s, torch::Tensor b1s,
+                                double lr, torch::Tensor snap) {
+  torch::Tensor loss;
+  HeadTailArgs hta = head_tail_args(x, h, w2s, b2s, y, loss);
+  const int B = (int)x.size(0), M = (int)x.size(1), H = (int)h.size(1);
+  for (auto* t : {&w1m, &b1m, &w2m, &b2m})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->scalar_type() == torch::kFloat, "masters must be fp32");
+  for (auto* t : {&w1s, &b1s})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->scalar_type() == torch::kBFloat16,
+                "shadows must be bf16");
+  TORCH_CHECK(w1m.numel() == (long)M * H && b1m.numel() == H &&
+              w1s.numel() == w1m.numel() && b1s.numel() == H,
+              "W1/b1 shape mismatch");
+  TORCH_CHECK(w2m.numel() == w2s.numel() && b2m.numel() == b2s.numel(),
+              "W2/b2 master/shadow shape mismatch");
+  if (snap.numel() > 0) {
+    // W2/b2 as mlp_fwd_snap's launch copied them: no ticket needed
+    TORCH_CHECK(snap.is_cuda() && snap.is_contiguous() &&
+                snap.scalar_type() == torch::kBFloat16 &&
+                snap.numel() >= kSnapB2Off + 16 &&
+                w2s.numel() <= kSnapB2Off,
+                "snap must be mlp_fwd_snap's buffer");
+    hta.w2 = snap.data_ptr();
+    hta.b2 = (const bf16_t*)snap.data_ptr() + kSnapB2Off;
+    hta.ticket = nullptr;
+  } else {
+    hta.ticket = head_tail_ticket(x.device());
+  }
+  SmallSgdArgs sga = {};
+  sga.pmw = (float*)w1m.data_ptr();
+  sga.psw = w1s.data_ptr();
+  sga.pmb = (float*)b1m.data_ptr();
+  sga.psb = b1s.data_ptr();
+  sga.pm2w = (float*)w2m.data_ptr();
+  sga.ps2w = w2s.data_ptr();
+  sga.pm2b = (float*)b2m.data_ptr();
+  sga.ps2b = b2s.data_ptr();
+  sga.lr = (float)lr;
+  sga.n2w = (int)w2m.numel();
+  sga.n2b = (int)b2m.numel();
+  launch_mlp_head_tail((const bf16_t*)x.data_ptr(), &hta, nullptr, nullptr,
+                       false, M, H, B, &sga, cur_stream());
+  return loss;
+}
+
+// grads mode of the same kernel (the distributed worker path): dW1,
+// db1, dW2, db2 are stored in the flat grad buffer's dtype (fp32 or
+// bf16, all four alike). Returns the mean loss.
+torch::Tensor mlp_head_tail_grads(torch::Tensor x, torch::Tensor h,
+                                  torch::Tensor w2, torch::Tensor b2,
+                                  torch::Tensor y, torch::Tensor dw1,
+                                  torch::Tensor db1, torch::Tensor dw2,
+                                  torch::Tensor db2) {
+  torch::Tensor loss;
+  HeadTailArgs hta = head_tail_args(x, h, w2, b2, y, loss);
+  const int B = (int)x.size(0), M = (int)x.size(1), H = (int)h.size(1);
+  const auto gt = dw1.scalar_type();
+  TORCH_CHECK(gt == torch::kFloat32 || gt == torch::kBFloat16,
+              "grads must be fp32 or bf16");
+  for (auto* t : {&dw1, &db1, &dw2, &db2})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->scalar_type() == gt, "grads must share one dtype");
+  TORCH_CHECK(dw1.numel() == (long)M * H && db1.numel() == H &&
+              dw2.numel() == w2.numel() && db2.numel() == b2.numel(),
+              "grad shape mismatch");
+  hta.dw2 = dw2.data_ptr();
+  hta.db2 = db2.data_ptr();
+  launch_mlp_head_tail((const bf16_t*)x.data_ptr(), &hta, dw1.data_ptr(),
+                       db1.data_ptr(), gt == torch::kFloat32, M, H, B,
+                       nullptr, cur_stream());
+  return loss;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_sgd", &fused_sgd, "fused SGD apply + bf16 shadow",
         py::arg("param"), py::arg("grad"), py::arg("momentum_buf"),
@@ -1737,6 +1928,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_group_fwd_multi", &bn_group_fwd_multi);
   m.def("gemm_sgd", &gemm_sgd);
   m.def("mlp_tail_sgd", &mlp_tail_sgd);
+  m.def("mlp_head_tail_sgd", &mlp_head_tail_sgd);
+  m.def("mlp_fwd_snap", &mlp_fwd_snap);
+  m.def("mlp_head_tail_grads", &mlp_head_tail_grads);
   m.def("gemm_sgd_pair", &gemm_sgd_pair);
   m.def("add_n", &add_n);
   m.def("bn_group_bwd_multi", &bn_group_bwd_multi);

@@ -30,6 +30,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "mlp_head.h"
 
 namespace {
 
@@ -322,12 +323,25 @@ void gemm_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B,
 // 1-elem/thread variant for SMALL outputs (mnist fwd: mn = 10k gave
 // only 10 WGs at 4 elems/thread — the reduce was WG-count
 // latency-bound, not bandwidth-bound; 4x the blocks cut it ~2x)
+// sj (optional, dst != null): the last, mostly idle block also copies
+// two small bf16 ranges (see SnapArgs) — a side job for the NEXT launch
+struct SnapJob {
+  const __bf16* s0; const __bf16* s1;
+  __bf16* dst;
+  int n0, n1, off1;
+};
+
 template <int ACT, bool BIAS, bool OUTF32>
 __global__ __launch_bounds__(256)
 void splitk_reduce_small_kernel(const float* __restrict__ ws,
                                 const void* __restrict__ bias,
                                 bool bias_bf16, void* __restrict__ Cout,
-                                long mn, int ldc, int nslice) {
+                                long mn, int ldc, int nslice, SnapJob sj) {
+  if (sj.dst != nullptr && blockIdx.x == gridDim.x - 1) {
+    for (int j = threadIdx.x; j < sj.n0; j += 256) sj.dst[j] = sj.s0[j];
+    for (int j = threadIdx.x; j < sj.n1; j += 256)
+      sj.dst[sj.off1 + j] = sj.s1[j];
+  }
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= mn) return;
   float v = 0.f;
@@ -430,6 +444,107 @@ struct SmallSgd {
   float lr;
   int n2w, n2b;
 };
+
+// transpose-read fragment out of a k-major wave image (see tr_frag;
+// same provider-lane scheme, 32-wide rows via sptr)
+DEVINL bf16x8 trs_frag(const __bf16* S, int ko, int lane) {
+  const int kq = ko + ((lane & 15) >> 2);
+  const int c = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  bf16x4 f0 = tr_read(sptr(S, kq, c));
+  bf16x4 f1 = tr_read(sptr(S, kq + 4, c));
+  return __builtin_shufflevector(f0, f1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// colsum partials of one wave: lane (kk, half) holds 16 columns of B
+// row kk; xor-shuffle tree over the 32 rows, then lane kk==0 of each
+// half parks its 16 sums in csw[32]
+DEVINL void small_cs_reduce(const float* csp, float* csw, int lane) {
+  float c2[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) c2[j] = csp[j];
+#pragma unroll
+  for (int off = 1; off < 32; off <<= 1)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) c2[j] += __shfl_xor(c2[j], off, 64);
+  if ((lane & 31) == 0) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) csw[(lane >> 5) * 16 + j] = c2[j];
+  }
+}
+
+// fused W1/b1 apply: ALL FOUR waves split the 16 output values
+// (4 each, straight from the LDS partials) — the wave0-only form
+// serialized the master-read/store latency on one wave per block
+// and measured SLOWER than the separate wide sgd_kernel
+DEVINL void small_sgd_w1b1(const SmallSgd& sg, const float (*red)[64 * 16],
+                           const float (*csred)[32], bool cs, int m0, int n0,
+                           int M, int N, int ldc, int w, int lane) {
+  const int n = n0 + (lane & 31);
+  if (n < N) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int v = w * 4 + u;
+      const int m = m0 + ((v >> 2) << 3) + ((lane >> 5) << 2) + (v & 3);
+      if (m >= M) continue;
+      const float x = red[0][lane * 16 + v] + red[1][lane * 16 + v] +
+                      red[2][lane * 16 + v] + red[3][lane * 16 + v];
+      const long idx = (long)m * ldc + n;
+      const float pv = sg.pmw[idx] - sg.lr * x;
+      sg.pmw[idx] = pv;
+      sg.psw[idx] = f2bf(pv);
+    }
+  }
+  if (cs && w == 0 && blockIdx.x == 0 && lane < 32) {
+    const int nn = n0 + lane;
+    if (nn < N && sg.pmb != nullptr) {
+      const float sv = csred[0][lane] + csred[1][lane] + csred[2][lane] +
+                       csred[3][lane];
+      const float pv = sg.pmb[nn] - sg.lr * sv;
+      sg.pmb[nn] = pv;
+      sg.psb[nn] = f2bf(pv);
+    }
+  }
+}
+
+// plain store epilogue (wave 0): cross-wave sum, bias/relu, fp32 or
+// bf16 out, and the colsum by blockIdx.x == 0
+DEVINL void small_store(const float (*red)[64 * 16],
+                        const float (*csred)[32], bool cs,
+                        const void* bias, bool bias_bf16, void* Cout,
+                        bool out_f32, int relu, void* colsum_out,
+                        bool cs_f32, int m0, int n0, int M, int N, int ldc,
+                        int lane) {
+  f32x16 tot;
+#pragma unroll
+  for (int v = 0; v < 16; ++v)
+    tot[v] = red[0][lane * 16 + v] + red[1][lane * 16 + v] +
+             red[2][lane * 16 + v] + red[3][lane * 16 + v];
+  const int n = n0 + (lane & 31);
+  if (n < N) {
+    float bvv = 0.f;
+    if (bias != nullptr)
+      bvv = bias_bf16 ? (float)((const __bf16*)bias)[n]
+                      : ((const float*)bias)[n];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const int m = m0 + ((v >> 2) << 3) + ((lane >> 5) << 2) + (v & 3);
+      if (m >= M) continue;
+      float x = tot[v] + bvv;
+      if (relu) x = x > 0.f ? x : 0.f;
+      if (out_f32) ((float*)Cout)[(long)m * ldc + n] = x;
+      else ((__bf16*)Cout)[(long)m * ldc + n] = (__bf16)x;
+    }
+  }
+  if (cs && blockIdx.x == 0 && lane < 32) {
+    const int nn = n0 + lane;
+    if (nn < N) {
+      const float sv = csred[0][lane] + csred[1][lane] + csred[2][lane] +
+                       csred[3][lane];
+      if (cs_f32) ((float*)colsum_out)[nn] = sv;
+      else ((__bf16*)colsum_out)[nn] = (__bf16)sv;
+    }
+  }
+}
 
 template <bool TA, bool CS>
 __global__ __launch_bounds__(256)
@@ -548,16 +663,6 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
     }
   };
 
-  // transpose-read fragment out of a k-major wave image (see tr_frag;
-  // same provider-lane scheme, 32-wide rows via sptr)
-  auto trs_frag = [&](const __bf16* S, int ko) {
-    const int kq = ko + ((lane & 15) >> 2);
-    const int c = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-    bf16x4 f0 = tr_read(sptr((__bf16*)S, kq, c));
-    bf16x4 f1 = tr_read(sptr((__bf16*)S, kq + 4, c));
-    return __builtin_shufflevector(f0, f1, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
-
   load_a(ks);
   commit();
   for (int k0 = ks; k0 < ke; k0 += BK) {
@@ -566,9 +671,9 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh) {
       const int ko = kh * 16 + ((lane >> 5) << 3);
-      bf16x8 a = TA ? trs_frag(Aw, ko)
+      bf16x8 a = TA ? trs_frag(Aw, ko, lane)
                     : *(const bf16x8*)sptr(Aw, lane & 31, ko);
-      bf16x8 b = trs_frag(Bw, ko);
+      bf16x8 b = trs_frag(Bw, ko, lane);
       *(f32x16*)acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
           a, b, *(f32x16*)acc, 0, 0, 0);
     }
@@ -578,19 +683,7 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
   // cross-wave reduce (the only barrier) + epilogue by wave 0
 #pragma unroll
   for (int v = 0; v < 16; ++v) red[w][lane * 16 + v] = ((float*)acc)[v];
-  if (CS && blockIdx.x == 0) {
-    float c2[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) c2[j] = csp[j];
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) c2[j] += __shfl_xor(c2[j], off, 64);
-    if (kk == 0) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) csred[w][half * 16 + j] = c2[j];
-    }
-  }
+  if (CS && blockIdx.x == 0) small_cs_reduce(csp, csred[w], lane);
   __syncthreads();
   if (sg.pm2w != nullptr && w == 1 && blockIdx.x == 0 && blockIdx.y == 0) {
     // classifier apply: ~1k elems on one idle wave; runs strictly
@@ -652,70 +745,380 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
     }
   }
   if (sg.pmw != nullptr) {
-    // fused W1/b1 apply: ALL FOUR waves split the 16 output values
-    // (4 each, straight from the LDS partials) — the wave0-only form
-    // serialized the master-read/store latency on one wave per block
-    // and measured SLOWER than the separate wide sgd_kernel
-    const int n = n0 + (lane & 31);
-    if (n < N) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int v = w * 4 + u;
-        const int m = m0 + ((v >> 2) << 3) + ((lane >> 5) << 2) + (v & 3);
-        if (m >= M) continue;
-        const float x = red[0][lane * 16 + v] + red[1][lane * 16 + v] +
-                        red[2][lane * 16 + v] + red[3][lane * 16 + v];
-        const long idx = (long)m * ldc + n;
-        const float pv = sg.pmw[idx] - sg.lr * x;
-        sg.pmw[idx] = pv;
-        sg.psw[idx] = f2bf(pv);
-      }
-    }
-    if (CS && w == 0 && blockIdx.x == 0 && lane < 32) {
-      const int nn = n0 + lane;
-      if (nn < N && sg.pmb != nullptr) {
-        const float sv = csred[0][lane] + csred[1][lane] + csred[2][lane] +
-                         csred[3][lane];
-        const float pv = sg.pmb[nn] - sg.lr * sv;
-        sg.pmb[nn] = pv;
-        sg.psb[nn] = f2bf(pv);
-      }
-    }
+    small_sgd_w1b1(sg, red, csred, CS, m0, n0, M, N, ldc, w, lane);
     return;
   }
   if (w != 0) return;
-  f32x16 tot;
-#pragma unroll
-  for (int v = 0; v < 16; ++v)
-    tot[v] = red[0][lane * 16 + v] + red[1][lane * 16 + v] +
-             red[2][lane * 16 + v] + red[3][lane * 16 + v];
-  const int n = n0 + (lane & 31);
-  if (n < N) {
-    float bvv = 0.f;
-    if (bias != nullptr)
-      bvv = bias_bf16 ? (float)((const __bf16*)bias)[n]
-                      : ((const float*)bias)[n];
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const int m = m0 + ((v >> 2) << 3) + ((lane >> 5) << 2) + (v & 3);
-      if (m >= M) continue;
-      float x = tot[v] + bvv;
-      if (relu) x = x > 0.f ? x : 0.f;
-      if (out_f32) ((float*)Cout)[(long)m * ldc + n] = x;
-      else ((__bf16*)Cout)[(long)m * ldc + n] = (__bf16)x;
-    }
-  }
-  if (CS && blockIdx.x == 0 && lane < 32) {
-    const int nn = n0 + lane;
-    if (nn < N) {
-      const float sv = csred[0][lane] + csred[1][lane] + csred[2][lane] +
-                       csred[3][lane];
-      if (cs_f32) ((float*)colsum_out)[nn] = sv;
-      else ((__bf16*)colsum_out)[nn] = (__bf16)sv;
-    }
-  }
+  small_store(red, csred, CS, bias, bias_bf16, Cout, out_f32, relu,
+              colsum_out, cs_f32, m0, n0, M, N, ldc, lane);
 }
 
+// ------------------------------------------------ fused head + tail
+//
+// mnist step, launches 3 and 4 in one: every block of the dW1 tail
+// (grid ceil(M/32) x ceil(H/32)) RECOMPUTES the slice of the classifier
+// head it consumes instead of waiting for a one-workgroup head kernel
+// to write dh. Wave w of gemm_small_kernel<TA> at K = B <= 128 consumes
+// exactly dh rows 32w..32w+31 of its 32-column N tile, and the head's
+// wave ownership is the same rows, so each wave stages its 32 rows of
+// h and the 2 KB classifier into wave-private LDS, runs the shared
+// logits / softmax / dh phases (mlp_head.h) and writes the bf16 dh
+// fragment straight into its k-major Bs image — no block barrier on
+// the way, and dh, dlogits, dW2 and db2 never touch global memory.
+// From there it IS gemm_small_kernel: two MFMAs per wave, the red
+// barrier, and the W1/b1 apply (APPLY) or the dW1/db1 store.
+//
+// One block additionally produces dW2 = h^T dls, db2 and the loss from
+// the full hs/dls images every block holds after the barrier (same
+// MFMA order over rows and the same 16-partial db2 order as the head;
+// the transposed fragments come from the row-major images via
+// ds_read_b64_tr_b16). !APPLY: block (0,0) stores them. APPLY: every
+// block read the live W2/b2 shadow at its start, so they may only be
+// overwritten once all blocks have read — an arrival ticket without
+// any spinning picks the block that arrives last: after the barrier
+// (all four waves' W2/b2 loads have landed in LDS) one lane draws an
+// agent-scope fetch_add ticket, the block applies its own W1 tile
+// while the ticket is in flight, and whoever drew nblocks-1 does the
+// classifier work and stores 0 back (stream order makes the
+// self-reset sufficient for the next launch and for graph replay).
+// The ticket measured ~5 us (16.4 us vs 11.4 us for the grads mode
+// that needs none): the classifier work is serialized behind the last
+// arrival. So where the step's preceding launch can take a 2 KB
+// snapshot of W2/b2 (the small stripe reduce, SnapJob), the kernel
+// reads the snapshot instead (ticket == null) and a fixed block
+// applies to the live shadow concurrently — no atomics at all. The
+// ticket stays for shapes whose fwd GEMM has no such reduce launch.
+// Unlike the rejected split-K last-arriver epilogue, the ticket's last
+// arriver reads NOTHING another block wrote in this launch — no stripe
+// pull, no acquire of foreign data, no L1-staleness hazard; the ticket
+// only orders other blocks' completed READS before its writes.
+struct HeadTail {
+  const __bf16* h;       // [B, H] relu output
+  const __bf16* w2;      // [H, C] (APPLY: live shadow, or its snapshot)
+  const bf16_t* b2;      // [C]
+  const long* labels;    // [B]
+  float* loss;
+  void* dw2;             // !APPLY: [H, C] / [C] in the grad dtype
+  void* db2;
+  unsigned* ticket;      // APPLY: zeroed device word; null = snapshot
+  float scale;
+  int C;
+};
+
+template <bool APPLY, bool GF32>
+__global__ __launch_bounds__(256)
+void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
+                          void* __restrict__ Cout,
+                          void* __restrict__ colsum_out,
+                          int M, int N, int K, SmallSgd sg) {
+  __shared__ __align__(16) __bf16 hs[HB * HP];       // [row][k], all waves
+  __shared__ __align__(16) __bf16 wtp[4][CP * HP];   // per wave [c][k]
+  __shared__ __align__(16) __bf16 wpd[4][32 * CP];   // per wave, N tile rows
+  __shared__ __align__(16) __bf16 dls[HB * CP];      // [row][c]
+  __shared__ float ls[HB * LSP];
+  __shared__ float lsum[HB];
+  __shared__ __align__(16) __bf16 As[4][32 * BK];
+  __shared__ __align__(16) __bf16 Bs[4][32 * BK];
+  __shared__ float red[4][64 * 16];
+  __shared__ float csred[4][32];
+  __shared__ float db2p[CP * 16];
+  __shared__ unsigned tick;
+  const int t = threadIdx.x;
+  const int lane = t & 63;
+  const int w = t >> 6;
+  const int m0 = blockIdx.x * 32;
+  const int n0 = blockIdx.y * 32;
+  const int C = ht.C;
+  const int ks = w * 32;              // kq == 32 for every K <= 128
+  const int ke = min(ks + 32, K);
+  __bf16* Aw = As[w];
+  __bf16* Bw = Bs[w];
+  __bf16* wtw = wtp[w];
+  __bf16* wpw = wpd[w];
+  const int kk = lane & 31;
+  const int half = lane >> 5;
+
+  // 1. the x chunk (gemm_small's load_a, A half) flies under the head
+  bf16x8 ra0 = {}, ra1 = {};
+  {
+    const int gk = ks + kk;
+    const int gm = m0 + half * 16;
+    if (gk < ke) {
+      const __bf16* src = X + (long)gk * M + gm;
+      if ((M & 7) == 0 && gm + 16 <= M) {
+        ra0 = *(const bf16x8*)src;
+        ra1 = *(const bf16x8*)(src + 8);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (gm + j < M) ra0[j] = src[j];
+          if (gm + 8 + j < M) ra1[j] = src[8 + j];
+        }
+      }
+    }
+  }
+  // 2. this wave's 32 rows of h (b64 chunks, two rows per pass; zeros
+  // beyond B and H so the LDS image needs no separate clear), the
+  // classifier (one hidden row per lane), bias and labels — every
+  // global load is issued before the first LDS store waits on one
+  bf16x4 hv[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int id = i * 64 + lane;
+    const int r = ks + (id >> 5);
+    const int c4 = (id & 31) * 4;
+    hv[i] = bf16x4{};
+    if (r < K && c4 < N) hv[i] = *(const bf16x4*)&ht.h[(long)r * N + c4];
+  }
+  __bf16 wv[2][CP];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int hr = lane + q * 64;
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+      wv[q][c] = (__bf16)0.f;
+      if (hr < N && c < C) wv[q][c] = ht.w2[hr * C + c];
+    }
+  }
+  const float bc = kk < C ? bf2f(ht.b2[kk]) : 0.f;
+  int label = 0;
+  if (lane < 32 && ks + lane < K) label = (int)ht.labels[ks + lane];
+
+  {
+    const bf16x8 z8 = {};
+    for (int i = lane * 8; i < CP * HP; i += 64 * 8) *(bf16x8*)&wtw[i] = z8;
+    *(bf16x8*)&wpw[lane * 8] = z8;
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int id = i * 64 + lane;
+    *(bf16x4*)&hs[(ks + (id >> 5)) * HP + (id & 31) * 4] = hv[i];
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int hr = lane + q * 64;
+    if (hr < N) {
+      const bool mine = hr >= n0 && hr < n0 + 32;
+#pragma unroll
+      for (int c = 0; c < CP; ++c) {
+        if (c < C) {
+          wtw[c * HP + hr] = wv[q][c];
+          if (mine) wpw[(hr - n0) * CP + c] = wv[q][c];
+        }
+      }
+    }
+  }
+
+  // 3. logits for rows ks..ks+31 (the wave's DS pipe is in order, so
+  // the fragment reads see the stores above without a barrier)
+  {
+    const f32x16v acc = head_logits_tile(
+        &hs[(ks + kk) * HP], kk < CP ? &wtw[kk * HP] : nullptr, lane);
+    head_store_logits(ls, acc, ks, bc, lane);
+  }
+  // 4. softmax + dlogits, one lane per row; rows >= B stay zero
+  if (lane < 32) {
+    const int row = ks + lane;
+    const bf16x8 z8 = {};
+    *(bf16x8*)&dls[row * CP] = z8;
+    *(bf16x8*)&dls[row * CP + 8] = z8;
+    float neglogp = 0.f;
+    if (row < K)
+      neglogp = head_softmax_row(
+          &ls[row * LSP], C, label, ht.scale,
+          [&](int c, float d) { dls[row * CP + c] = (__bf16)d; });
+    lsum[row] = neglogp;
+  }
+  // 5. dh fragment -> relu mask -> bf16 -> the k-major Bs image, where
+  // commit() would have put the loaded dh (zeros beyond B and H)
+  {
+    const f32x16v acc =
+        head_dh_tile(&dls[(ks + kk) * CP], &wpw[kk * CP], lane);
+    const int colh = n0 + kk;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const int rl = head_frag_row(v, lane);
+      const float hval = (float)hs[(ks + rl) * HP + colh];
+      const float m =
+          (ks + rl < K && colh < N && hval > 0.f) ? acc[v] : 0.f;
+      const bf16_t r = f2bf(m);
+      *sptr(Bw, rl, kk) = *(const __bf16*)&r;
+    }
+  }
+  *(bf16x8*)sptr(Aw, kk, half * 16) = ra0;
+  *(bf16x8*)sptr(Aw, kk, half * 16 + 8) = ra1;
+  // 6. db1 colsum from the bf16 dh values, same partials and tree as
+  // gemm_small's commit()/small_cs_reduce
+  if (blockIdx.x == 0) {
+    const bf16x8 rb0 = *(const bf16x8*)sptr(Bw, kk, half * 16);
+    const bf16x8 rb1 = *(const bf16x8*)sptr(Bw, kk, half * 16 + 8);
+    float csp[16] = {};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      csp[j] += (float)rb0[j];
+      csp[8 + j] += (float)rb1[j];
+    }
+    small_cs_reduce(csp, csred[w], lane);
+  }
+  // 7. dW1 partial of this wave's K span
+  f32x4 acc[4] = {};
+  if (ks < ke) {
+#pragma unroll
+    for (int kh = 0; kh < 2; ++kh) {
+      const int ko = kh * 16 + ((lane >> 5) << 3);
+      bf16x8 a = trs_frag(Aw, ko, lane);
+      bf16x8 b = trs_frag(Bw, ko, lane);
+      *(f32x16*)acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          a, b, *(f32x16*)acc, 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < 16; ++v) red[w][lane * 16 + v] = ((float*)acc)[v];
+  __syncthreads();
+
+  bool head_block;
+  const bool ticketed = APPLY && ht.ticket != nullptr;
+  if (APPLY) {
+    if (ticketed && t == 0)
+      tick = __hip_atomic_fetch_add(ht.ticket, 1u, __ATOMIC_ACQ_REL,
+                                    __HIP_MEMORY_SCOPE_AGENT);
+    small_sgd_w1b1(sg, red, csred, true, m0, n0, M, N, N, w, lane);
+    if (ticketed) {
+      __syncthreads();
+      head_block = tick == gridDim.x * gridDim.y - 1;
+    } else {
+      // w2/b2 are a snapshot the preceding launch took: nobody reads
+      // the live shadow here, so a fixed block applies right away, in
+      // parallel with the other tiles (the ragged last M tile has the
+      // least W1 work and no b1 apply)
+      head_block = blockIdx.x == gridDim.x - 1 && blockIdx.y == 0;
+    }
+  } else {
+    if (gridDim.x * gridDim.y >= 32) {
+      if (w == 0)
+        small_store(red, csred, true, nullptr, false, Cout, GF32, 0,
+                    colsum_out, GF32, m0, n0, M, N, N, lane);
+    } else {
+      // below 32 tiles gemm_bias_act runs dW1 on gemm_kernel<tn,CS>,
+      // not on gemm_small_kernel: K chained through ONE 16x16x32
+      // accumulator per element and a serial colsum over k. Reproduce
+      // that order from the four waves' k-major images (all complete
+      // after the barrier) so grads mode equals the two-kernel path
+      // bit for bit at every tile count. Wave w owns one 16x16 quarter.
+      const int wr = w >> 1, wc = w & 1;
+      const int kfrag = (lane >> 4) * 8;
+      const int kr = kfrag + ((lane & 15) >> 2);
+      const int cq = 4 * (lane & 3);
+      f32x4 c4 = {};
+      for (int q = 0; q * 32 < K; ++q) {
+        bf16x4 a0 = tr_read(sptr(As[q], kr, wr * 16 + cq));
+        bf16x4 a1 = tr_read(sptr(As[q], kr + 4, wr * 16 + cq));
+        bf16x4 b0 = tr_read(sptr(Bs[q], kr, wc * 16 + cq));
+        bf16x4 b1 = tr_read(sptr(Bs[q], kr + 4, wc * 16 + cq));
+        c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7),
+            __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7), c4,
+            0, 0, 0);
+      }
+      const int col = n0 + wc * 16 + (lane & 15);
+      if (col < N) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = m0 + wr * 16 + (lane >> 4) * 4 + r;
+          if (row >= M) continue;
+          float v = c4[r];
+          v += 0.f;                      // gemm_kernel's bias-less add
+          if (GF32) ((float*)Cout)[(long)row * N + col] = v;
+          else ((__bf16*)Cout)[(long)row * N + col] = (__bf16)v;
+        }
+      }
+      if (blockIdx.x == 0 && t < 32 && n0 + t < N) {
+        float cs = 0.f;
+        for (int q = 0; q * 32 < K; ++q)
+#pragma unroll
+          for (int k2 = 0; k2 < 32; ++k2) cs += (float)*sptr(Bs[q], k2, t);
+        if (GF32) ((float*)colsum_out)[n0 + t] = cs;
+        else ((__bf16*)colsum_out)[n0 + t] = (__bf16)cs;
+      }
+    }
+    head_block = blockIdx.x == 0 && blockIdx.y == 0;
+  }
+  if (!head_block) return;
+
+  // 8. classifier grads by ONE block: dW2[H,C] = h^T @ dls, K = B over
+  // the eight 16-row steps, wave w owns hidden rows 32w..32w+31
+  {
+    f32x16v acc2 = {};
+    const int kr = (lane & 15) >> 2;
+    const int ca = ks + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    const int cb = 4 * (lane & 3);
+    const bool bzero = ((lane >> 4) & 1) != 0;   // classes 16..31
+#pragma unroll
+    for (int kh = 0; kh < HB / 16; ++kh) {
+      const int kq = kh * 16 + ((lane >> 5) << 3) + kr;
+      bf16x4 a0 = tr_read(&hs[kq * HP + ca]);
+      bf16x4 a1 = tr_read(&hs[(kq + 4) * HP + ca]);
+      bf16x4 b0 = tr_read(&dls[kq * CP + cb]);
+      bf16x4 b1 = tr_read(&dls[(kq + 4) * CP + cb]);
+      bf16x8 a = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
+      bf16x8 bv = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
+      if (bzero) bv = bf16x8{};
+      acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bv, acc2, 0, 0, 0);
+    }
+    if (kk < C) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const int hrow = ks + head_frag_row(v, lane);
+        if (hrow < N) {
+          const int idx = hrow * C + kk;
+          if (APPLY) {
+            // bf16-rounded like the grads the head used to store
+            const float pv = sg.pm2w[idx] - sg.lr * bf2f(f2bf(acc2[v]));
+            sg.pm2w[idx] = pv;
+            sg.ps2w[idx] = f2bf(pv);
+          } else if (GF32) {
+            ((float*)ht.dw2)[idx] = acc2[v];
+          } else {
+            ((bf16_t*)ht.dw2)[idx] = f2bf(acc2[v]);
+          }
+        }
+      }
+    }
+  }
+  // db2[c] = sum_b dls[b][c], 16 partial lanes per class as in the head
+  if (t < C * 16) {
+    const int c = t >> 4, part = t & 15;
+    float s = 0.f;
+    for (int b2 = part; b2 < K; b2 += 16) s += (float)dls[b2 * CP + c];
+    db2p[t] = s;
+  }
+  __syncthreads();
+  if (t < C) {
+    float s = 0.f;
+#pragma unroll
+    for (int p2 = 0; p2 < 16; ++p2) s += db2p[t * 16 + p2];
+    if (APPLY) {
+      const float pv = sg.pm2b[t] - sg.lr * bf2f(f2bf(s));
+      sg.pm2b[t] = pv;
+      sg.ps2b[t] = f2bf(pv);
+    } else if (GF32) {
+      ((float*)ht.db2)[t] = s;
+    } else {
+      ((bf16_t*)ht.db2)[t] = f2bf(s);
+    }
+  }
+  // mean loss: the head's 256-slot LDS tree (slots >= 128 are zero
+  // there) replayed on wave 0 — same pairs, same order
+  if (w == 0) {
+    float v = (lsum[lane] + 0.f) + (lsum[lane + 64] + 0.f);
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s, 64);
+    if (lane == 0) *ht.loss = v / K;
+  }
+  if (ticketed && t == 0)
+    __hip_atomic_store(ht.ticket, 0u, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // split-K phase 2 fused with the SGD apply (the NMF factor update):
 // instead of materializing the fp32 gradient and re-reading it in a
@@ -758,7 +1161,12 @@ void launch_gemm(const bf16_t* A, const bf16_t* B, const void* bias,
                  bool bias_bf16, void* C, bool out_f32, const bf16_t* aux,
                  void* colsum_out, float* ws, int* cnt, int kc, int nslice,
                  int M, int N, int K, int lda, int ldb, int ldc, bool ta,
-                 bool tb, int act, int veca, int vecb, hipStream_t stream) {
+                 bool tb, int act, int veca, int vecb, hipStream_t stream,
+                 const SnapArgs* snap, bool* snap_taken) {
+  // snap: side copy for the next launch, done only where the small
+  // stripe reduce runs; *snap_taken tells the caller whether it was
+  SnapJob sj = {};
+  if (snap_taken) *snap_taken = false;
   const bool sk = nslice > 1;
   dim3 grid(ceil_div(N, BN), ceil_div(M, BM), sk ? nslice : 1);
   dim3 block(256);
@@ -839,11 +1247,17 @@ void launch_gemm(const bf16_t* A, const bf16_t* B, const void* bias,
     dim3 rgrid((unsigned)(small_r ? (mn + 255) / 256
                                   : ((mn + 3) / 4 + 255) / 256));
     dim3 rblock(256);
+    if (small_r && snap != nullptr) {
+      sj.s0 = (const __bf16*)snap->s0; sj.s1 = (const __bf16*)snap->s1;
+      sj.dst = (__bf16*)snap->dst;
+      sj.n0 = snap->n0; sj.n1 = snap->n1; sj.off1 = snap->off1;
+      if (snap_taken) *snap_taken = true;
+    }
 #define RLAUNCH(ACTv, BIASv, OUTv)                                          \
     do { if (small_r)                                                       \
       hipLaunchKernelGGL((splitk_reduce_small_kernel<ACTv, BIASv, OUTv>),   \
                          rgrid, rblock, 0, stream, ws, bias, bias_bf16, C,  \
-                         mn, ldc, nslice);                                  \
+                         mn, ldc, nslice, sj);                              \
     else                                                                    \
       hipLaunchKernelGGL((splitk_reduce_kernel<ACTv, BIASv, OUTv>), rgrid,  \
                          rblock, 0, stream, ws, bias, bias_bf16, C, mn,     \
@@ -910,6 +1324,45 @@ void launch_gemm_small(const bf16_t* A, const bf16_t* B, const void* bias,
   if (ta) { if (cs) GS(true, true); else GS(true, false); }
   else    { if (cs) GS(false, true); else GS(false, false); }
 #undef GS
+}
+
+// fused head + tail (see mlp_head_tail_kernel). sga != null: APPLY
+// (plain-SGD step, bf16-rounded classifier grads); else dW1/db1 and
+// dW2/db2 are stored in the grad dtype. Shape limits are checked by
+// the bindings.
+void launch_mlp_head_tail(const bf16_t* x, const HeadTailArgs* hta,
+                          void* dw1, void* db1, bool grads_f32, int M,
+                          int H, int B, const SmallSgdArgs* sga,
+                          hipStream_t stream) {
+  dim3 grid(ceil_div(M, 32), ceil_div(H, 32)), block(256);
+  HeadTail ht;
+  ht.h = (const __bf16*)hta->h;
+  ht.w2 = (const __bf16*)hta->w2;
+  ht.b2 = (const bf16_t*)hta->b2;
+  ht.labels = hta->labels;
+  ht.loss = hta->loss;
+  ht.dw2 = hta->dw2;
+  ht.db2 = hta->db2;
+  ht.ticket = hta->ticket;
+  ht.scale = hta->scale;
+  ht.C = hta->C;
+  SmallSgd sg = {};
+  if (sga) {
+    sg.pmw = sga->pmw; sg.psw = (bf16_t*)sga->psw;
+    sg.pmb = sga->pmb; sg.psb = (bf16_t*)sga->psb;
+    sg.pm2w = sga->pm2w; sg.ps2w = (bf16_t*)sga->ps2w;
+    sg.pm2b = sga->pm2b; sg.ps2b = (bf16_t*)sga->ps2b;
+    sg.lr = sga->lr; sg.n2w = sga->n2w; sg.n2b = sga->n2b;
+    hipLaunchKernelGGL((mlp_head_tail_kernel<true, false>), grid, block, 0,
+                       stream, (const __bf16*)x, ht, nullptr, nullptr, M, H,
+                       B, sg);
+  } else if (grads_f32) {
+    hipLaunchKernelGGL((mlp_head_tail_kernel<false, true>), grid, block, 0,
+                       stream, (const __bf16*)x, ht, dw1, db1, M, H, B, sg);
+  } else {
+    hipLaunchKernelGGL((mlp_head_tail_kernel<false, false>), grid, block, 0,
+                       stream, (const __bf16*)x, ht, dw1, db1, M, H, B, sg);
+  }
 }
 
 

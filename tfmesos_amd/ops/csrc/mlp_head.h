@@ -1,0 +1,90 @@
+// Shared device phases of the mnist classifier head: the logits tile,
+// the rowwise softmax/dlogits and the dh tile. Included by the
+// single-launch head (softmax_xent.hip, mlp_head_mfma_kernel) and by
+// the fused head+tail kernel (gemm.hip, mlp_head_tail_kernel), which
+// recomputes them per wave — ONE definition, so the two paths cannot
+// drift apart in arithmetic order (results are compared bit for bit).
+#pragma once
+
+#include "common.h"
+
+typedef __attribute__((ext_vector_type(16))) float f32x16v;
+
+constexpr int HB = 128;        // padded B/H tile
+constexpr int HP = 136;        // hs row stride (8-elem pad, 16B aligned)
+constexpr int CP = 16;         // padded class dim
+// fp32 logits staging: stride 17 (a 16-dword stride put every lane
+// of a softmax row-read on 2 of 32 banks — 32-way conflicts)
+constexpr int LSP = CP + 1;
+
+// row (within the 32-row tile) of accumulator slot v in a 32x32 MFMA
+// D fragment; the column is lane & 31
+DEVINL int head_frag_row(int v, int lane) {
+  return ((v >> 2) << 3) + ((lane >> 5) << 2) + (v & 3);
+}
+
+// logits tile [32 rows, 32 padded classes] = hs rows @ w, K = HB in
+// eight MFMA steps. arow: this lane's hs row (lane & 31 of the tile);
+// brow: this lane's w^T row (class lane & 31), or null for a class
+// beyond the padded image — an all-zero B fragment.
+DEVINL f32x16v head_logits_tile(const __bf16* arow, const __bf16* brow,
+                                int lane) {
+  f32x16v acc = {};
+#pragma unroll
+  for (int kh = 0; kh < HB / 16; ++kh) {
+    const int k0 = kh * 16 + ((lane >> 5) << 3);
+    bf16x8 a = *(const bf16x8*)&arow[k0];
+    bf16x8 bv = {};
+    if (brow != nullptr) bv = *(const bf16x8*)&brow[k0];
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bv, acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// add the class bias and park the tile in the fp32 staging (rows
+// row0.. of ls); bc is this lane's bias (0 beyond C)
+DEVINL void head_store_logits(float* ls, const f32x16v& acc, int row0,
+                              float bc, int lane) {
+  const int col = lane & 31;
+  if (col < CP) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v)
+      ls[(row0 + head_frag_row(v, lane)) * LSP + col] = acc[v] + bc;
+  }
+}
+
+// rowwise softmax + dlogits over C <= 16 classes (scalar, one lane per
+// row): emit(c, d) receives d = (p - onehot) * scale per class;
+// returns -log p[label]
+template <class F>
+DEVINL float head_softmax_row(const float* lr, int C, int label,
+                              float scale, F emit) {
+  float neglogp = 0.f;
+  float mx = -3.4e38f;
+  for (int c = 0; c < C; ++c) mx = fmaxf(mx, lr[c]);
+  float sum = 0.f;
+  float e[16];
+  for (int c = 0; c < C; ++c) {
+    e[c] = __expf(lr[c] - mx);
+    sum += e[c];
+  }
+  const float inv = 1.f / sum;
+  for (int c = 0; c < C; ++c) {
+    const float p = e[c] * inv;
+    const float d = (p - (c == label ? 1.f : 0.f)) * scale;
+    emit(c, d);
+    if (c == label) neglogp = -__logf(fmaxf(p, 1e-30f));
+  }
+  return neglogp;
+}
+
+// dh tile [32 rows, 32 hidden cols] = dls rows @ w^T, K = CP (one
+// MFMA). drow: this lane's dls row; wrow: this lane's wpad row (hidden
+// column lane & 31 of the tile). Unmasked — the caller applies h > 0.
+DEVINL f32x16v head_dh_tile(const __bf16* drow, const __bf16* wrow,
+                            int lane) {
+  bf16x8 a = *(const bf16x8*)&drow[(lane >> 5) << 3];
+  bf16x8 bv = *(const bf16x8*)&wrow[(lane >> 5) << 3];
+  f32x16v acc = {};
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bv, acc, 0, 0, 0);
+}

@@ -5,6 +5,7 @@
 // class dimension (10 for mnist, up to 4096 supported) is reduced with
 // wave shuffles — no LDS round trip, no separate log-softmax pass.
 #include "common.h"
+#include "mlp_head.h"
 
 namespace {
 
@@ -247,8 +248,6 @@ void mlp_head_fused_kernel(const bf16_t* __restrict__ h,
 // (100 of 512 threads active). Cuts the mnist step's critical path
 // from {logits GEMM, softmax, dh GEMM} = three ~5-7 us launches to one
 // kernel.
-typedef __attribute__((ext_vector_type(16))) float f32x16v;
-
 // phase-stamp debug hook (tools/headbench.py --phases): wall_clock64
 // per phase per workgroup, written when the pointer is armed
 __device__ unsigned long long* g_head_dbg = nullptr;
@@ -258,9 +257,8 @@ DEVINL void head_stamp(int t, int phase) {
     g_head_dbg[blockIdx.x * 16 + phase] = wall_clock64();
 }
 
-constexpr int HB = 128;        // padded B/H tile
-constexpr int HP = 136;        // hs row stride (8-elem pad, 16B aligned)
-constexpr int CP = 16;         // padded class dim
+// tile constants (HB, HP, CP, LSP) and the logits / softmax / dh
+// phases live in mlp_head.h, shared with the fused head+tail kernel
 
 // dw2/db2 (optional): the weight/bias grads of the classifier are
 // computed IN the same kernel (both operands already live in LDS),
@@ -300,10 +298,7 @@ void mlp_head_mfma_kernel(const bf16_t* __restrict__ h,
   // gathers per thread — the dh phase alone measured 4.4 us of the
   // 11 us kernel, see tools/headbench.py --phases)
   __shared__ __align__(16) __bf16 hsT[HB * HP];
-  // fp32 logits staging: stride 17 (a 16-dword stride put every lane
-  // of a softmax row-read on 2 of 32 banks — 32-way conflicts)
-  constexpr int LSP = CP + 1;
-  __shared__ float ls[HB * LSP];
+  __shared__ float ls[HB * LSP];   // fp32 logits staging
   __shared__ float lsum[256];
   const int t = threadIdx.x;
   const int lane = t & 63;
@@ -384,24 +379,11 @@ void mlp_head_mfma_kernel(const bf16_t* __restrict__ h,
 
   // logits[B,C] = hs @ w: wave wr owns rows 32wr..32wr+31
   {
-    f32x16v acc = {};
-#pragma unroll
-    for (int kh = 0; kh < HB / 16; ++kh) {
-      const int k0 = kh * 16 + ((lane >> 5) << 3);
-      bf16x8 a = *(const bf16x8*)&hs[(wr * 32 + (lane & 31)) * HP + k0];
-      bf16x8 bv = *(const bf16x8*)&wtp[(lane & 31) * HP + k0];
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bv, acc, 0, 0, 0);
-    }
+    const f32x16v acc = head_logits_tile(
+        &hs[(wr * 32 + (lane & 31)) * HP], &wtp[(lane & 31) * HP], lane);
     const int col = lane & 31;
-    if (col < CP) {
-      const float bc = col < C ? bf2f(bias[col]) : 0.f;
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const int row = wr * 32 + ((v >> 2) << 3) + ((lane >> 5) << 2) +
-                        (v & 3);
-        ls[row * LSP + col] = acc[v] + bc;
-      }
-    }
+    const float bc = col < C ? bf2f(bias[col]) : 0.f;
+    head_store_logits(ls, acc, wr * 32, bc, lane);
   }
   __syncthreads();
   head_stamp(t, 3);
@@ -414,25 +396,13 @@ void mlp_head_mfma_kernel(const bf16_t* __restrict__ h,
   const bool wg1 = blockIdx.x + 1 == gridDim.x;
   float neglogp = 0.f;
   if (t < B) {
-    const float* lr = &ls[t * LSP];
-    float mx = -3.4e38f;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, lr[c]);
-    float sum = 0.f;
-    float e[16];
-    for (int c = 0; c < C; ++c) {
-      e[c] = __expf(lr[c] - mx);
-      sum += e[c];
-    }
-    const float inv = 1.f / sum;
     const int label = (int)labels[t];
-    for (int c = 0; c < C; ++c) {
-      const float p = e[c] * inv;
-      const float d = (p - (c == label ? 1.f : 0.f)) * scale;
-      dls[t * CP + c] = (__bf16)d;
-      dlsT[c * HP + t] = (__bf16)d;
-      if (wg0) dlogits[(long)t * C + c] = f2bf(d);
-      if (c == label) neglogp = -__logf(fmaxf(p, 1e-30f));
-    }
+    neglogp = head_softmax_row(
+        &ls[t * LSP], C, label, scale, [&](int c, float d) {
+          dls[t * CP + c] = (__bf16)d;
+          dlsT[c * HP + t] = (__bf16)d;
+          if (wg0) dlogits[(long)t * C + c] = f2bf(d);
+        });
   }
   lsum[t] = neglogp;
   __syncthreads();
@@ -442,14 +412,10 @@ void mlp_head_mfma_kernel(const bf16_t* __restrict__ h,
   // 32wr..+31, loops the four 32-wide H column tiles; K = C (one MFMA)
   if (wg0) {
     const int arow = wr * 32 + (lane & 31);
-    bf16x8 a = *(const bf16x8*)&dls[arow * CP + ((lane >> 5) << 3)];
 #pragma unroll
     for (int ct = 0; ct < HB / 32; ++ct) {
-      bf16x8 bv =
-          *(const bf16x8*)&wpad[(ct * 32 + (lane & 31)) * CP +
-                                ((lane >> 5) << 3)];
-      f32x16v acc = {};
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bv, acc, 0, 0, 0);
+      const f32x16v acc = head_dh_tile(
+          &dls[arow * CP], &wpad[(ct * 32 + (lane & 31)) * CP], lane);
       const int colh = ct * 32 + (lane & 31);
       if (colh < H) {
         // relu mask: 4 b64 reads of the transposed copy (one per
@@ -462,8 +428,7 @@ void mlp_head_mfma_kernel(const bf16_t* __restrict__ h,
           mk[g] = *(const bf16x4*)&hsT[colh * HP + rbase + g * 8];
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int row = wr * 32 + ((v >> 2) << 3) + ((lane >> 5) << 2) +
-                          (v & 3);
+          const int row = wr * 32 + head_frag_row(v, lane);
           if (row < B) {
             const float m =
                 (float)mk[v >> 2][v & 3] > 0.f ? acc[v] : 0.f;
