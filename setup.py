@@ -28,6 +28,7 @@ sources = [
     os.path.join(CSRC, "sparse_apply.hip"),
     os.path.join(CSRC, "partition.hip"),
     os.path.join(CSRC, "coalesce.hip"),
+    os.path.join(CSRC, "hash.hip"),
     os.path.join(CSRC, "elementwise.hip"),
 ]
 

@@ -18,11 +18,15 @@ combiner sum / mean, optional weights) and the same sparse applies fed
 bag gradients (``offsets=``); and the routing of requests to a row-sharded
 table (TF's partitioned variable): shard_partition, permute_rows,
 shard_bag_offsets, bag_coefficients; and the worker-side coalescing of a row
-request (TF's unique / unsorted_segment_sum): coalesce_ids, segment_sum_rows.
+request (TF's unique / unsorted_segment_sum): coalesce_ids, segment_sum_rows;
+and the key index of hashed embedding tables (TF's MutableHashTable):
+HashIndex, hash_find, hash_find_or_insert, hash_rebuild, hash_gather,
+hash_init_rows, hash_init_new_rows.
 """
 
 import collections
 
+import numpy as np
 import torch
 
 _EXT = None
@@ -641,6 +645,293 @@ def segment_sum_rows(rows, perm, seg, num, out_dtype=None):
     out = torch.zeros(num, rows.shape[1])
     out.index_add_(0, of[keep], rows.float().index_select(0, perm[keep]))
     return out.to(out_dtype)
+
+
+# ------------------------------------------------- hashed embedding tables
+#
+# An index from arbitrary int64 keys to the dense rows 0 .. size-1 of a
+# table of fixed capacity (TF's MutableHashTable / dynamic embedding
+# variable): the features of CTR and recommender models are 64-bit hashes or
+# raw categorical ids of an open vocabulary, not row numbers. Every int64
+# value is a key except HASH_EMPTY (INT64_MIN), which is treated as absent
+# and never inserted. Rows are handed out in allocation order; row_keys[r]
+# is the key that owns row r. GPU: csrc/hash.hip — an open-addressing slot
+# array (load <= 0.5), integer atomics only, identical results from run to
+# run, nothing read back. CPU (the reference): a Python dict.
+
+HASH_EMPTY = -2 ** 63
+HASH_KEY_SPACE = 2 ** 62    # ``rows=`` of a row-sharded hashed table
+_HASH_GOLD = 0x9E3779B97F4A7C15
+_U64 = 2 ** 64
+
+
+def _mix64(z):
+    """The splitmix64 finaliser on a numpy uint64 ARRAY (array arithmetic
+    wraps silently; numpy scalars would warn)."""
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _u64_array(keys):
+    return keys.detach().cpu().contiguous().numpy().view(np.uint64)
+
+
+def _hash_keys_check(keys):
+    if keys.dim() != 1 or keys.dtype != torch.int64:
+        raise ValueError("keys must be int64 [n]")
+    if keys.numel() >= 2 ** 31:
+        raise ValueError("hash index: n must be below 2**31")
+
+
+def hash_slots(capacity):
+    """Slots H of an index of ``capacity`` rows: the smallest power of two
+    that is at least 2 * capacity and at least 64 (one wave's probe)."""
+    H = 64
+    while H < 2 * capacity:
+        H *= 2
+    return H
+
+
+def hash_home(keys, slots):
+    """The home slot of every key in an array of ``slots`` slots (a power of
+    two): splitmix64-finaliser(key as uint64) & (slots - 1). int64 [n] on
+    the CPU. An internal detail of the index — exposed so that a test can
+    build long probe chains; no result of any op depends on it."""
+    _hash_keys_check(keys)
+    if slots < 1 or slots & (slots - 1):
+        raise ValueError("slots must be a power of two, got %r" % (slots,))
+    h = _mix64(_u64_array(keys)) & np.uint64(slots - 1)
+    return torch.from_numpy(h.astype(np.int64))
+
+
+class HashIndex(object):
+    """Key index of a hashed table with ``capacity`` rows on ``device``.
+
+    row_keys int64 [capacity] (HASH_EMPTY behind ``size``), size and dropped
+    int64 [1] on the device (reading them is the caller's sync), and on a
+    GPU the slot arrays slot_keys / slot_rows int64 [hash_slots(capacity)].
+    On the CPU the reference keeps a dict instead of slot arrays."""
+
+    def __init__(self, capacity, device="cpu"):
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError("capacity must be >= 1, got %d" % capacity)
+        self.device = torch.device(device)
+        self.capacity = capacity
+        self.row_keys = torch.full((capacity,), HASH_EMPTY,
+                                   dtype=torch.int64, device=self.device)
+        self.size = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.dropped = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._alloc_slots()
+
+    def _alloc_slots(self):
+        self._map = {}
+        self.slot_keys = self.slot_rows = None
+        if self.device.type != "cpu":
+            H = hash_slots(self.capacity)
+            self.slot_keys = torch.full((H,), HASH_EMPTY, dtype=torch.int64,
+                                        device=self.device)
+            self.slot_rows = torch.full((H,), -1, dtype=torch.int64,
+                                        device=self.device)
+
+    def reserve(self, capacity):
+        """Grow to ``capacity`` rows: larger row_keys and slot arrays, then
+        a rebuild. The key -> row mapping is unchanged; no host sync."""
+        capacity = int(capacity)
+        if capacity < self.capacity:
+            raise ValueError("reserve(%d): the index already has capacity %d "
+                             "(shrinking is not supported)"
+                             % (capacity, self.capacity))
+        if capacity == self.capacity:
+            return
+        row_keys = torch.full((capacity,), HASH_EMPTY, dtype=torch.int64,
+                              device=self.device)
+        row_keys[:self.capacity] = self.row_keys
+        self.row_keys = row_keys
+        self.capacity = capacity
+        self._alloc_slots()
+        hash_rebuild(self)
+
+    def assign(self, keys):
+        """Make ``keys`` (distinct, none HASH_EMPTY, at most capacity) the
+        owners of rows 0 .. len(keys)-1 (checkpoint load)."""
+        _hash_keys_check(keys)
+        n = keys.numel()
+        if n > self.capacity:
+            raise ValueError("%d keys do not fit capacity %d"
+                             % (n, self.capacity))
+        self.row_keys.fill_(HASH_EMPTY)
+        self.row_keys[:n] = keys.to(self.device)
+        self.size.fill_(n)
+        self.dropped.zero_()
+        hash_rebuild(self)
+
+
+def _hash_index_check(index, keys):
+    _hash_keys_check(keys)
+    if keys.device.type != index.device.type:
+        raise ValueError("keys are on %s, the index on %s"
+                         % (keys.device, index.device))
+
+
+@torch.no_grad()
+def hash_find(index, keys):
+    """rows int64 [n]: the row of keys[i], -1 when the key is absent (or
+    HASH_EMPTY). Read-only."""
+    _hash_index_check(index, keys)
+    if keys.is_cuda:
+        return _ext().hash_find(index.slot_keys, index.slot_rows,
+                                keys.contiguous())
+    get = index._map.get
+    return torch.tensor([get(k, -1) for k in keys.tolist()],
+                        dtype=torch.int64)
+
+
+@torch.no_grad()
+def hash_find_or_insert(index, keys):
+    """(rows int64 [n], is_new bool [n]). Like hash_find, but an absent key
+    gets the next free row: the new keys of one request receive rows size,
+    size + 1, ... in the order of their FIRST occurrence in the request and
+    every duplicate gets that row; is_new marks the one position (the first
+    occurrence) that allocated it. A key that would need a row >= capacity
+    gets -1 and ``dropped`` grows by the number of DISTINCT such keys of the
+    request; it gets a row on a later request once there is room
+    (``reserve``). HASH_EMPTY gives -1 and is not counted. Deterministic:
+    the GPU (csrc/hash.hip) equals this dict loop integer for integer."""
+    _hash_index_check(index, keys)
+    if keys.is_cuda:
+        rows, is_new = _ext().hash_find_or_insert(
+            index.slot_keys, index.slot_rows, index.row_keys, index.size,
+            index.dropped, keys.contiguous())
+        return rows, is_new
+    m, cap = index._map, index.capacity
+    size = int(index.size)
+    rows, fresh, lost = [], [], set()
+    for k in keys.tolist():
+        r = -1 if k == HASH_EMPTY else m.get(k)
+        if r is None:
+            if size < cap:
+                r = m[k] = size
+                index.row_keys[r] = k
+                size += 1
+                fresh.append(len(rows))
+            else:
+                r = -1
+                lost.add(k)
+        rows.append(r)
+    index.size.fill_(size)
+    index.dropped += len(lost)
+    is_new = torch.zeros(len(rows), dtype=torch.bool)
+    is_new[fresh] = True
+    return torch.tensor(rows, dtype=torch.int64), is_new
+
+
+@torch.no_grad()
+def hash_rebuild(index):
+    """Rebuild the key -> row mapping from row_keys[0:size] (after
+    ``reserve`` or a checkpoint load). GPU: clears the slot arrays and
+    inserts the keys with their known rows, no host sync."""
+    if index.device.type != "cpu":
+        _ext().hash_rebuild(index.slot_keys, index.slot_rows, index.row_keys,
+                            index.size)
+        return
+    n = int(index.size)
+    index._map = {k: r for r, k in enumerate(index.row_keys[:n].tolist())}
+
+
+def _rows_or_zero(table, rows):
+    """table[rows] with a zero row for every row outside [0, V) (CPU)."""
+    keep = (rows >= 0) & (rows < table.shape[0])
+    out = torch.zeros(rows.numel(), table.shape[1], dtype=table.dtype)
+    out[keep] = table.index_select(0, rows[keep])
+    return out
+
+
+@torch.no_grad()
+def hash_gather(index, table, keys):
+    """The serving pull: out[i] = table[row of keys[i]], a zero row for an
+    absent key — hash_find followed by embedding_gather, in ONE launch on
+    the GPU (one wave per key probes 64 slots per step and copies the row).
+    table bf16 [V,D]."""
+    _hash_index_check(index, keys)
+    if table.dim() != 2 or table.dtype != torch.bfloat16:
+        raise ValueError("hash_gather: table must be bf16 [V,D]")
+    if keys.is_cuda:
+        return _ext().hash_gather(index.slot_keys, index.slot_rows, table,
+                                  keys.contiguous())
+    return _rows_or_zero(table, hash_find(index, keys))
+
+
+def _hash_scale(dim):
+    return np.float32(dim ** -0.5)
+
+
+def hash_init_rows(keys, dim, seed, key_mul=1, key_add=0):
+    """The initial rows of ``keys``: fp32 [n, dim] on the CPU (the
+    reference of the init kernel, equal to it bit for bit). Column c of the
+    row of key k is a pure function of (seed, k, c) — not of insertion
+    order, capacity or sharding:
+
+        G = 0x9E3779B97F4A7C15
+        mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9
+                z = (z ^ z >> 27) * 0x94D049BB133111EB
+                return z ^ z >> 31                      (splitmix64)
+        k = key * key_mul + key_add
+        z = mix(mix(mix(seed + G) ^ k) + c * G)         (wrapping uint64)
+        value = float32(z >> 40) * 2**-24 * float32(dim ** -0.5)
+
+    The top 24 bits are an exact fp32 integer and the product by 2**-24 is
+    exact; the product by the scale is one fp32 rounding: uniform in
+    [0, dim**-0.5), the distribution of EmbeddingTable's rand / sqrt(dim).
+    key_mul / key_add turn the local key of a shard into its global key."""
+    _hash_keys_check(keys)
+    k = _u64_array(keys) * np.array([key_mul % _U64], dtype=np.uint64) \
+        + np.array([key_add % _U64], dtype=np.uint64)
+    a = _mix64(np.array([(seed + _HASH_GOLD) % _U64], dtype=np.uint64))
+    b = _mix64(a ^ k)
+    cols = np.arange(dim, dtype=np.uint64) * np.uint64(_HASH_GOLD)
+    z = _mix64(b[:, None] + cols[None, :])
+    u = (z >> np.uint64(40)).astype(np.float32)
+    return torch.from_numpy(u * np.float32(2.0 ** -24) * _hash_scale(dim))
+
+
+@torch.no_grad()
+def hash_init_new_rows(keys, rows, is_new, master, shadow, states, seed,
+                       key_mul=1, key_add=0):
+    """In place, for every position i with is_new[i] (a find_or_insert that
+    allocated rows[i]): master[rows[i]] = hash_init_rows(keys[i]), shadow
+    the bf16 of it, and a zero row in every tensor of ``states`` (at most
+    two). master fp32, shadow bf16, states fp32, all [V, D]. GPU: one
+    kernel, grid sized from n, nothing read back."""
+    _hash_keys_check(keys)
+    n = keys.numel()
+    if tuple(rows.shape) != (n,) or rows.dtype != torch.int64 or \
+            tuple(is_new.shape) != (n,) or is_new.dtype != torch.bool:
+        raise ValueError("hash_init_new_rows: need rows int64 [n] and is_new "
+                         "bool [n] for n = %d keys" % n)
+    if master.dim() != 2 or master.dtype != torch.float32 or \
+            shadow.dtype != torch.bfloat16 or shadow.shape != master.shape:
+        raise ValueError("hash_init_new_rows: master must be fp32 [V,D] and "
+                         "shadow bf16 [V,D]")
+    states = list(states)
+    if len(states) > 2 or any(s.dtype != torch.float32 or
+                              s.shape != master.shape for s in states):
+        raise ValueError("hash_init_new_rows: states must be at most two "
+                         "fp32 [V,D] tensors")
+    if master.is_cuda:
+        _ext().hash_init_new_rows(
+            keys.contiguous(), rows.contiguous(), is_new.contiguous(),
+            master, shadow, states, int(seed), int(key_mul), int(key_add),
+            float(_hash_scale(master.shape[1])))
+        return
+    sel = is_new & (rows >= 0) & (rows < master.shape[0])
+    r = rows[sel]
+    vals = hash_init_rows(keys[sel], master.shape[1], seed, key_mul, key_add)
+    master[r] = vals
+    shadow[r] = vals.to(torch.bfloat16)
+    for s in states:
+        s[r] = 0.0
 
 
 # ------------------------------------------------- sparse optimizer applies

@@ -80,6 +80,20 @@ long segment_scratch_rows(long);
 void launch_segment_sum_rows(const void*, bool, const long*, const long*,
                              float*, void*, bool, long, long, int,
                              hipStream_t);
+void launch_hash_find(const long*, const long*, const long*, long*, long,
+                      long, hipStream_t);
+void launch_hash_lookup(const long*, const long*, const long*, long*, long*,
+                        long*, int*, long, long, long, hipStream_t);
+void launch_hash_insert(const long*, const int*, const long*, long*, long*,
+                        long*, long*, long*, long*, bool*, long, long, long,
+                        hipStream_t);
+void launch_hash_rebuild(const long*, const long*, long*, long*, long, long,
+                         hipStream_t);
+void launch_hash_gather(const long*, const long*, const long*, const bf16_t*,
+                        bf16_t*, long, long, long, int, hipStream_t);
+void launch_hash_init_rows(const long*, const long*, const bool*, float*,
+                           bf16_t*, float*, float*, long, long, int, long,
+                           long, long, float, hipStream_t);
 void launch_relu_bwd(const bf16_t*, const bf16_t*, bf16_t*, long,
                      hipStream_t);
 void launch_add_n(const bf16_t* const*, int, bf16_t*, long, hipStream_t);
@@ -1188,6 +1202,164 @@ torch::Tensor segment_sum_rows(torch::Tensor rows, torch::Tensor perm,
   return out;
 }
 
+// ---- hashed embedding tables (hash.hip) ----------------------------------
+
+namespace {
+
+bool hash_i64(const torch::Tensor& t) {
+  return t.is_cuda() && t.scalar_type() == torch::kInt64 && t.dim() == 1 &&
+         t.is_contiguous();
+}
+
+// The slot arrays of an index: equal length, a power of two >= 64.
+long hash_slots(const torch::Tensor& slot_keys,
+                const torch::Tensor& slot_rows) {
+  TORCH_CHECK(hash_i64(slot_keys) && hash_i64(slot_rows) &&
+              slot_keys.numel() == slot_rows.numel(),
+              "hash: slot_keys and slot_rows must be contiguous i64 [H] on "
+              "GPU");
+  const long H = slot_keys.numel();
+  TORCH_CHECK(H >= 64 && (H & (H - 1)) == 0,
+              "hash: H must be a power of two >= 64");
+  return H;
+}
+
+long hash_keys(const torch::Tensor& keys) {
+  TORCH_CHECK(hash_i64(keys), "hash: keys must be contiguous i64 [n] on GPU");
+  TORCH_CHECK(keys.numel() < (long)INT_MAX, "hash: n must be below 2^31");
+  return keys.numel();
+}
+
+void hash_counters(const torch::Tensor& row_keys, const torch::Tensor& size,
+                   long H) {
+  TORCH_CHECK(hash_i64(row_keys) && hash_i64(size) && size.numel() == 1,
+              "hash: row_keys [capacity] and size [1] must be contiguous i64 "
+              "on GPU");
+  TORCH_CHECK(row_keys.numel() >= 1 && 2 * row_keys.numel() <= H,
+              "hash: need 1 <= capacity <= H / 2");
+}
+
+}  // namespace
+
+// rows [n]: the row of every key, -1 when absent. Read-only.
+torch::Tensor hash_find(torch::Tensor slot_keys, torch::Tensor slot_rows,
+                        torch::Tensor keys) {
+  const long H = hash_slots(slot_keys, slot_rows), n = hash_keys(keys);
+  auto rows = torch::empty({n}, keys.options());
+  if (n == 0) return rows;   // a zero-size grid is a launch error
+  launch_hash_find(keys.data_ptr<long>(), slot_keys.data_ptr<long>(),
+                   slot_rows.data_ptr<long>(), rows.data_ptr<long>(), n, H,
+                   cur_stream());
+  return rows;
+}
+
+// rows [n] and is_new bool [n]; absent keys get the rows size, size + 1, ..
+// in order of first occurrence while they are below capacity (hash.hip).
+// The scratch fill and the scan of the flags are plumbing; no host sync.
+std::vector<torch::Tensor> hash_find_or_insert(
+    torch::Tensor slot_keys, torch::Tensor slot_rows, torch::Tensor row_keys,
+    torch::Tensor size, torch::Tensor dropped, torch::Tensor keys) {
+  const long H = hash_slots(slot_keys, slot_rows), n = hash_keys(keys);
+  hash_counters(row_keys, size, H);
+  TORCH_CHECK(hash_i64(dropped) && dropped.numel() == 1,
+              "hash: dropped must be i64 [1] on GPU");
+  auto opt = keys.options();
+  auto rows = torch::empty({n}, opt);
+  auto is_new = torch::empty({n}, opt.dtype(torch::kBool));
+  if (n == 0) return {rows, is_new};
+  long S = 64;
+  while (S < 2 * n) S <<= 1;
+  // [0] keys, [1] smallest position: both start at INT64_MIN
+  auto scratch = torch::full({2, S}, (int64_t)LONG_MIN, opt);
+  auto flags = torch::empty({n}, opt.dtype(torch::kInt32));
+  long* sk = scratch.data_ptr<long>();
+  launch_hash_lookup(keys.data_ptr<long>(), slot_keys.data_ptr<long>(),
+                     slot_rows.data_ptr<long>(), rows.data_ptr<long>(), sk,
+                     sk + S, flags.data_ptr<int>(), n, H, S, cur_stream());
+  auto incl = torch::cumsum(flags, 0, torch::kInt64);
+  launch_hash_insert(keys.data_ptr<long>(), flags.data_ptr<int>(),
+                     incl.data_ptr<long>(), slot_keys.data_ptr<long>(),
+                     slot_rows.data_ptr<long>(), row_keys.data_ptr<long>(),
+                     size.data_ptr<long>(), dropped.data_ptr<long>(),
+                     rows.data_ptr<long>(), is_new.data_ptr<bool>(), n, H,
+                     row_keys.numel(), cur_stream());
+  return {rows, is_new};
+}
+
+// Clears the slot arrays and inserts row_keys[0:size] with their rows.
+void hash_rebuild(torch::Tensor slot_keys, torch::Tensor slot_rows,
+                  torch::Tensor row_keys, torch::Tensor size) {
+  const long H = hash_slots(slot_keys, slot_rows);
+  hash_counters(row_keys, size, H);
+  slot_keys.fill_((int64_t)LONG_MIN);
+  slot_rows.fill_(-1);
+  launch_hash_rebuild(row_keys.data_ptr<long>(), size.data_ptr<long>(),
+                      slot_keys.data_ptr<long>(), slot_rows.data_ptr<long>(),
+                      H, row_keys.numel(), cur_stream());
+}
+
+// out [n,D] bf16: the table row of every key, zeros on a miss; one launch.
+torch::Tensor hash_gather(torch::Tensor slot_keys, torch::Tensor slot_rows,
+                          torch::Tensor table, torch::Tensor keys) {
+  const long H = hash_slots(slot_keys, slot_rows), n = hash_keys(keys);
+  TORCH_CHECK(table.is_cuda() && table.dim() == 2 && table.is_contiguous() &&
+              table.scalar_type() == torch::kBFloat16,
+              "hash_gather: table must be contiguous bf16 [V,D] on GPU");
+  const long V = table.size(0), D = table.size(1);
+  TORCH_CHECK(D <= (long)INT_MAX, "hash_gather: D too large");
+  auto out = torch::empty({n, D}, table.options());
+  if (n == 0 || D == 0) return out;
+  launch_hash_gather(keys.data_ptr<long>(), slot_keys.data_ptr<long>(),
+                     slot_rows.data_ptr<long>(),
+                     (const bf16_t*)table.data_ptr(), (bf16_t*)out.data_ptr(),
+                     n, H, V, (int)D, cur_stream());
+  return out;
+}
+
+// Initial master / shadow rows and zeroed state rows for the positions of
+// a find_or_insert that allocated a row. states: 0, 1 or 2 fp32 [V,D].
+void hash_init_new_rows(torch::Tensor keys, torch::Tensor rows,
+                        torch::Tensor is_new, torch::Tensor master,
+                        torch::Tensor shadow,
+                        std::vector<torch::Tensor> states, long seed,
+                        long key_mul, long key_add, double scale) {
+  const long n = hash_keys(keys);
+  TORCH_CHECK(hash_i64(rows) && rows.numel() == n && is_new.is_cuda() &&
+              is_new.scalar_type() == torch::kBool && is_new.dim() == 1 &&
+              is_new.is_contiguous() && is_new.numel() == n,
+              "hash_init_new_rows: rows i64 [n] and is_new bool [n] must be "
+              "contiguous on GPU");
+  TORCH_CHECK(master.is_cuda() && master.dim() == 2 &&
+              master.is_contiguous() &&
+              master.scalar_type() == torch::kFloat32,
+              "hash_init_new_rows: master must be contiguous fp32 [V,D] on "
+              "GPU");
+  TORCH_CHECK(shadow.is_cuda() && shadow.is_contiguous() &&
+              shadow.scalar_type() == torch::kBFloat16 &&
+              shadow.sizes() == master.sizes(),
+              "hash_init_new_rows: shadow must be contiguous bf16 [V,D]");
+  TORCH_CHECK(states.size() <= 2, "hash_init_new_rows: at most 2 states");
+  float* sp[2] = {nullptr, nullptr};
+  for (size_t k = 0; k < states.size(); ++k) {
+    const auto& s = states[k];
+    TORCH_CHECK(s.is_cuda() && s.is_contiguous() &&
+                s.scalar_type() == torch::kFloat32 &&
+                s.sizes() == master.sizes(),
+                "hash_init_new_rows: states must be contiguous fp32 [V,D]");
+    sp[k] = s.data_ptr<float>();
+  }
+  const long V = master.size(0), D = master.size(1);
+  const long tiles = (D + 255) / 256;
+  TORCH_CHECK(D <= (long)INT_MAX && n * tiles / 4 < (long)INT_MAX,
+              "hash_init_new_rows: too large for one grid");
+  if (n == 0 || D == 0 || V == 0) return;
+  launch_hash_init_rows(keys.data_ptr<long>(), rows.data_ptr<long>(),
+                        is_new.data_ptr<bool>(), master.data_ptr<float>(),
+                        (bf16_t*)shadow.data_ptr(), sp[0], sp[1], n, V,
+                        (int)D, seed, key_mul, key_add, (float)scale,
+                        cur_stream());
+}
+
 torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor act) {
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16 &&
               dy.is_contiguous() && act.is_contiguous() &&
@@ -1980,6 +2152,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out[k] = sum of rows[perm[seg[k]:seg[k+1]]], rounded once",
         py::arg("rows"), py::arg("perm"), py::arg("seg"), py::arg("num"),
         py::arg("out_bf16"));
+  m.def("hash_find", &hash_find, "rows of int64 keys, -1 when absent",
+        py::arg("slot_keys"), py::arg("slot_rows"), py::arg("keys"));
+  m.def("hash_find_or_insert", &hash_find_or_insert,
+        "rows of int64 keys, absent keys get the next free rows: rows, is_new",
+        py::arg("slot_keys"), py::arg("slot_rows"), py::arg("row_keys"),
+        py::arg("size"), py::arg("dropped"), py::arg("keys"));
+  m.def("hash_rebuild", &hash_rebuild,
+        "clear the slots and insert row_keys[0:size]",
+        py::arg("slot_keys"), py::arg("slot_rows"), py::arg("row_keys"),
+        py::arg("size"));
+  m.def("hash_gather", &hash_gather,
+        "bf16 table rows of int64 keys, zeros when absent",
+        py::arg("slot_keys"), py::arg("slot_rows"), py::arg("table"),
+        py::arg("keys"));
+  m.def("hash_init_new_rows", &hash_init_new_rows,
+        "initial master/shadow/state rows of newly allocated rows",
+        py::arg("keys"), py::arg("rows"), py::arg("is_new"),
+        py::arg("master"), py::arg("shadow"), py::arg("states"),
+        py::arg("seed"), py::arg("key_mul"), py::arg("key_add"),
+        py::arg("scale"));
   m.def("relu_bwd", &relu_bwd);
   m.def("colsum", &colsum, py::arg("x"), py::arg("out"));
 }

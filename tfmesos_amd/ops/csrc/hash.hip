@@ -1,0 +1,372 @@
+// Hashed embedding tables: a device-resident index from arbitrary int64 keys
+// to the dense rows 0 .. size-1 of a table of fixed capacity (TF's
+// MutableHashTable / dynamic embedding variable on the PS), the serving
+// gather through it, and the per-key row initialiser.
+//
+// Layout. H slots, H a power of two >= max(64, 2 * capacity): slot_keys[H]
+// (EMPTY = INT64_MIN, the one value that is not a key) and slot_rows[H].
+// The maximum load of 0.5 is a DESIGN CHOICE (short linear-probe chains at
+// 16 bytes per slot), not a measured optimum. home(key) = mix64(key) &
+// (H - 1), linear probing, no deletion: a key sits before the first EMPTY
+// slot of its probe sequence. Rows are numbered in allocation order and
+// row_keys[r] is the key that owns row r; WHERE a key hashes to is visible
+// to nothing outside this file. size and dropped are int64 device words;
+// no launcher reads anything back.
+//
+// Between two calls the slot array holds ONLY published (key, row) pairs:
+// a key that found no room (row >= capacity) never enters it, so the array
+// cannot fill with rowless keys and every probe ends at an EMPTY slot.
+//
+// find_or_insert(keys [n]) — four kernels, one lane per position, and one
+// scan; no sort, no float atomics, and no loop that waits for another
+// thread's store (every value a kernel needs from another thread was
+// written by an EARLIER kernel):
+//   1. lookup: rows[i] = the row of keys[i] or -1. An absent key is
+//      deduplicated in a per-call scratch table of S >= 2n slots (filled
+//      with EMPTY by the binding): 64-bit atomicCAS(EMPTY -> key) claims a
+//      slot, a loser that reads back its own key joins it, and an unsigned
+//      64-bit atomicMin records the smallest position per slot (EMPTY as an
+//      unsigned number, 2^63, lies above every position).
+//   2. flags: flag[i] = 1 where i is that smallest position — the first
+//      occurrence of a new key in the request.
+//   *  the inclusive scan of the flags is plumbing (torch.cumsum in the
+//      binding): incl[i] - 1 is the rank of the new key among the
+//      request's new keys, in order of first occurrence.
+//   3. insert: a flagged position whose row = size + rank is below capacity
+//      inserts (key, row) — the keys are distinct, so a plain CAS probe —,
+//      writes row_keys[row] and is_new[i] = 1.
+//   4. resolve: positions still at -1 look their key up again (duplicates
+//      of a new key find the row its first occurrence published in 3);
+//      lane 0 adds min(new, room) to size and the rest to dropped.
+//   Which scratch slot or hash slot a racing key lands in may differ from
+//   run to run; rows, is_new, row_keys, size and dropped cannot.
+//
+// hash_gather (serving): one wave per key. The wave reads 64 consecutive
+// slots per step (one per lane), ballots "is my key" and "is EMPTY", takes
+// the row from the first matching lane or stops at an EMPTY one, then
+// copies the bf16 row (8 bytes per lane when D % 4 == 0 and the bases are
+// 8-byte aligned) or writes zeros on a miss: one launch per pull.
+//
+// Row initialiser: value(seed, k, c) =
+//     float(mix64(mix64(mix64(seed + G) ^ k) + c * G) >> 40) * 2^-24 * scale
+// with G = 0x9E3779B97F4A7C15, mix64 the splitmix64 finaliser, k =
+// key * key_mul + key_add (the GLOBAL key of a shard-local one), all in
+// wrapping uint64; the 24-bit integer and the product by 2^-24 are exact in
+// fp32, the product by scale is one fp32 rounding. One wave per (position,
+// 256-column tile) writes master, shadow and zeroed state rows for the
+// positions with is_new set. Every bound is checked; grids are sized
+// from n.
+#include "common.h"
+
+#include <climits>
+
+#include "tile.h"
+
+namespace {
+
+constexpr int BLOCK = 256;
+constexpr int WAVES = 4;   // waves per block of the wave-per-item kernels
+constexpr long EMPTY = LONG_MIN;
+constexpr unsigned long long GOLD = 0x9E3779B97F4A7C15ull;
+
+typedef unsigned long long u64;
+
+DEVINL u64 mix64(u64 z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// slots: a power of two
+DEVINL long home_slot(long key, long slots) {
+  return (long)(mix64((u64)key) & (u64)(slots - 1));
+}
+
+// Read-only probe: the row of key, -1 when absent (or EMPTY).
+DEVINL long probe_find(const long* __restrict__ slot_keys,
+                       const long* __restrict__ slot_rows, long key, long H) {
+  if (key == EMPTY) return -1;
+  long s = home_slot(key, H);
+  for (long t = 0; t < H; ++t) {
+    const long k = slot_keys[s];
+    if (k == key) return slot_rows[s];
+    if (k == EMPTY) return -1;
+    s = (s + 1) & (H - 1);
+  }
+  return -1;
+}
+
+// Claims a slot for key (or joins the slot that holds it): the slot, -1
+// when all `slots` are taken by other keys.
+DEVINL long probe_claim(long* __restrict__ slot_keys, long key, long slots) {
+  long s = home_slot(key, slots);
+  for (long t = 0; t < slots; ++t) {
+    const u64 old = atomicCAS((u64*)&slot_keys[s], (u64)EMPTY, (u64)key);
+    if (old == (u64)EMPTY || old == (u64)key) return s;
+    s = (s + 1) & (slots - 1);
+  }
+  return -1;
+}
+
+__global__ __launch_bounds__(BLOCK) void find_kernel(
+    const long* __restrict__ keys, const long* __restrict__ slot_keys,
+    const long* __restrict__ slot_rows, long* __restrict__ rows, long n,
+    long H) {
+  const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  rows[i] = probe_find(slot_keys, slot_rows, keys[i], H);
+}
+
+// find_or_insert 1: lookup, and dedup of the absent keys in the scratch.
+__global__ __launch_bounds__(BLOCK) void lookup_kernel(
+    const long* __restrict__ keys, const long* __restrict__ slot_keys,
+    const long* __restrict__ slot_rows, long* __restrict__ rows,
+    long* __restrict__ skeys, long* __restrict__ spos, long n, long H,
+    long S) {
+  const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const long key = keys[i];
+  const long r = probe_find(slot_keys, slot_rows, key, H);
+  rows[i] = r;
+  if (r >= 0 || key == EMPTY) return;
+  const long s = probe_claim(skeys, key, S);
+  if (s >= 0) atomicMin((u64*)&spos[s], (u64)i);   // always: S >= 2n
+}
+
+// find_or_insert 2: first occurrences of the new keys.
+__global__ __launch_bounds__(BLOCK) void flag_kernel(
+    const long* __restrict__ keys, const long* __restrict__ rows,
+    const long* __restrict__ skeys, const long* __restrict__ spos,
+    int* __restrict__ flags, long n, long S) {
+  const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const long key = keys[i];
+  int flag = 0;
+  if (rows[i] < 0 && key != EMPTY) {
+    long s = home_slot(key, S);
+    for (long t = 0; t < S; ++t) {
+      const long k = skeys[s];
+      if (k == key) { flag = spos[s] == i; break; }
+      if (k == EMPTY) break;   // cannot happen: kernel 1 claimed it
+      s = (s + 1) & (S - 1);
+    }
+  }
+  flags[i] = flag;
+}
+
+// find_or_insert 3: publish the new keys that have room.
+__global__ __launch_bounds__(BLOCK) void insert_kernel(
+    const long* __restrict__ keys, const int* __restrict__ flags,
+    const long* __restrict__ incl, long* __restrict__ slot_keys,
+    long* __restrict__ slot_rows, long* __restrict__ row_keys,
+    const long* __restrict__ size, bool* __restrict__ is_new, long n, long H,
+    long capacity) {
+  const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  bool fresh = false;
+  if (flags[i]) {
+    const long row = size[0] + incl[i] - 1;
+    if (row >= 0 && row < capacity) {
+      const long key = keys[i];
+      const long s = probe_claim(slot_keys, key, H);
+      if (s >= 0) {   // always: at most capacity <= H / 2 keys
+        slot_rows[s] = row;
+        row_keys[row] = key;
+        fresh = true;
+      }
+    }
+  }
+  is_new[i] = fresh;
+}
+
+// find_or_insert 4: the rows of this request's new keys; the counters.
+__global__ __launch_bounds__(BLOCK) void resolve_kernel(
+    const long* __restrict__ keys, const long* __restrict__ slot_keys,
+    const long* __restrict__ slot_rows, const long* __restrict__ incl,
+    long* __restrict__ rows, long* __restrict__ size,
+    long* __restrict__ dropped, long n, long H, long capacity) {
+  const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  if (rows[i] < 0) rows[i] = probe_find(slot_keys, slot_rows, keys[i], H);
+  if (i == 0) {   // no lane of this kernel reads size
+    const long fresh = incl[n - 1], old = size[0];
+    const long room = capacity > old ? capacity - old : 0;
+    const long added = fresh < room ? fresh : room;
+    size[0] = old + added;
+    dropped[0] += fresh - added;
+  }
+}
+
+// row_keys[0:size] into a cleared slot array.
+__global__ __launch_bounds__(BLOCK) void rebuild_kernel(
+    const long* __restrict__ row_keys, const long* __restrict__ size,
+    long* __restrict__ slot_keys, long* __restrict__ slot_rows, long H,
+    long capacity) {
+  const long r = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (r >= capacity || r >= size[0]) return;
+  const long key = row_keys[r];
+  if (key == EMPTY) return;
+  const long s = probe_claim(slot_keys, key, H);
+  if (s >= 0) slot_rows[s] = r;
+}
+
+template <int VEC>
+__global__ __launch_bounds__(WAVES * WAVE) void hash_gather_kernel(
+    const long* __restrict__ keys, const long* __restrict__ slot_keys,
+    const long* __restrict__ slot_rows, const bf16_t* __restrict__ table,
+    bf16_t* __restrict__ out, long n, long H, long V, int D) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const long w = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (w >= n) return;   // wave-uniform
+  const long key = keys[w];
+  long row = -1;
+  if (key != EMPTY) {
+    const long base = home_slot(key, H);
+    for (long st = 0; st < H; st += WAVE) {
+      const long s = (base + st + lane) & (H - 1);
+      const long k = slot_keys[s];
+      const unsigned long long hit = __ballot(k == key);
+      const unsigned long long gap = __ballot(k == EMPTY);
+      if (hit) {
+        const int b = __ffsll(hit) - 1;
+        if (!gap || b < __ffsll(gap) - 1) row = __shfl(slot_rows[s], b);
+        break;
+      }
+      if (gap) break;
+    }
+  }
+  const bool live = row >= 0 && row < V;
+  const bf16_t* src = table + (live ? row : 0) * D;
+  bf16_t* dst = out + w * D;
+  if constexpr (VEC == 4) {
+    for (int c = lane * 4; c < D; c += WAVE * 4) {
+      bf16x4 v = {};
+      if (live) v = *(const bf16x4*)(const __bf16*)(src + c);
+      *(bf16x4*)(__bf16*)(dst + c) = v;
+    }
+  } else {
+    for (int c = lane; c < D; c += WAVE)
+      dst[c] = live ? src[c] : f2bf(0.f);
+  }
+}
+
+DEVINL float init_value(u64 b, int col, float scale) {
+  const u64 z = mix64(b + (u64)col * GOLD);
+  return (float)(unsigned)(z >> 40) * 0x1p-24f * scale;
+}
+
+// One wave per (position, 256-column tile); s1 / s2 may be null.
+template <int VEC>
+__global__ __launch_bounds__(WAVES * WAVE) void init_rows_kernel(
+    const long* __restrict__ keys, const long* __restrict__ rows,
+    const bool* __restrict__ is_new, float* __restrict__ master,
+    bf16_t* __restrict__ shadow, float* __restrict__ s1,
+    float* __restrict__ s2, long n, long V, int D, int tiles, long seed,
+    long key_mul, long key_add, float scale) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const long w = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (w >= n * tiles) return;   // wave-uniform
+  const long i = w / tiles;
+  const int c0 = (int)(w % tiles) * TILE;
+  if (!is_new[i]) return;
+  const long row = rows[i];
+  if (row < 0 || row >= V) return;
+  const u64 k = (u64)keys[i] * (u64)key_mul + (u64)key_add;
+  const u64 b = mix64(mix64((u64)seed + GOLD) ^ k);
+  float v[ACC], zero[ACC];
+#pragma unroll
+  for (int e = 0; e < ACC; ++e) {
+    const int col = VEC == 4 ? c0 + lane * 4 + e : c0 + e * WAVE + lane;
+    v[e] = init_value(b, col, scale);
+    zero[e] = 0.f;
+  }
+  st_tile<float, VEC>(master + row * D, c0, lane, D, v);
+  st_tile<bf16_t, VEC>(shadow + row * D, c0, lane, D, v);
+  if (s1) st_tile<float, VEC>(s1 + row * D, c0, lane, D, zero);
+  if (s2) st_tile<float, VEC>(s2 + row * D, c0, lane, D, zero);
+}
+
+inline dim3 lanes_grid(long n) {
+  return dim3((unsigned)((n + BLOCK - 1) / BLOCK));
+}
+
+}  // namespace
+
+// keys [n], n > 0 -> rows [n].
+void launch_hash_find(const long* keys, const long* slot_keys,
+                      const long* slot_rows, long* rows, long n, long H,
+                      hipStream_t stream) {
+  hipLaunchKernelGGL(find_kernel, lanes_grid(n), dim3(BLOCK), 0, stream, keys,
+                     slot_keys, slot_rows, rows, n, H);
+}
+
+// Kernels 1 and 2. skeys / spos: int64 [S] filled with INT64_MIN, S a power
+// of two >= 2n; flags int32 [n]. n > 0.
+void launch_hash_lookup(const long* keys, const long* slot_keys,
+                        const long* slot_rows, long* rows, long* skeys,
+                        long* spos, int* flags, long n, long H, long S,
+                        hipStream_t stream) {
+  hipLaunchKernelGGL(lookup_kernel, lanes_grid(n), dim3(BLOCK), 0, stream,
+                     keys, slot_keys, slot_rows, rows, skeys, spos, n, H, S);
+  hipLaunchKernelGGL(flag_kernel, lanes_grid(n), dim3(BLOCK), 0, stream, keys,
+                     rows, skeys, spos, flags, n, S);
+}
+
+// Kernels 3 and 4. incl: int64 inclusive scan of flags; is_new bool [n].
+void launch_hash_insert(const long* keys, const int* flags, const long* incl,
+                        long* slot_keys, long* slot_rows, long* row_keys,
+                        long* size, long* dropped, long* rows, bool* is_new,
+                        long n, long H, long capacity, hipStream_t stream) {
+  hipLaunchKernelGGL(insert_kernel, lanes_grid(n), dim3(BLOCK), 0, stream,
+                     keys, flags, incl, slot_keys, slot_rows, row_keys, size,
+                     is_new, n, H, capacity);
+  hipLaunchKernelGGL(resolve_kernel, lanes_grid(n), dim3(BLOCK), 0, stream,
+                     keys, slot_keys, slot_rows, incl, rows, size, dropped, n,
+                     H, capacity);
+}
+
+// slot_keys filled with INT64_MIN by the caller; capacity > 0.
+void launch_hash_rebuild(const long* row_keys, const long* size,
+                         long* slot_keys, long* slot_rows, long H,
+                         long capacity, hipStream_t stream) {
+  hipLaunchKernelGGL(rebuild_kernel, lanes_grid(capacity), dim3(BLOCK), 0,
+                     stream, row_keys, size, slot_keys, slot_rows, H,
+                     capacity);
+}
+
+// table bf16 [V,D] -> out bf16 [n,D]; n, D > 0.
+void launch_hash_gather(const long* keys, const long* slot_keys,
+                        const long* slot_rows, const bf16_t* table,
+                        bf16_t* out, long n, long H, long V, int D,
+                        hipStream_t stream) {
+  const dim3 grid((unsigned)((n + WAVES - 1) / WAVES));
+  const uintptr_t bases = (uintptr_t)table | (uintptr_t)out;
+  if ((D % 4) == 0 && (bases % 8) == 0)
+    hipLaunchKernelGGL(hash_gather_kernel<4>, grid, dim3(WAVES * WAVE), 0,
+                       stream, keys, slot_keys, slot_rows, table, out, n, H,
+                       V, D);
+  else
+    hipLaunchKernelGGL(hash_gather_kernel<1>, grid, dim3(WAVES * WAVE), 0,
+                       stream, keys, slot_keys, slot_rows, table, out, n, H,
+                       V, D);
+}
+
+// master fp32 / shadow bf16 [V,D], s1 / s2 fp32 [V,D] or null; n, D > 0.
+void launch_hash_init_rows(const long* keys, const long* rows,
+                           const bool* is_new, float* master, bf16_t* shadow,
+                           float* s1, float* s2, long n, long V, int D,
+                           long seed, long key_mul, long key_add, float scale,
+                           hipStream_t stream) {
+  const int tiles = (D + TILE - 1) / TILE;
+  const dim3 grid((unsigned)((n * tiles + WAVES - 1) / WAVES));
+  const uintptr_t bases = (uintptr_t)master | (uintptr_t)shadow |
+                          (uintptr_t)s1 | (uintptr_t)s2;
+  if ((D % 4) == 0 && (bases % 16) == 0)
+    hipLaunchKernelGGL(init_rows_kernel<4>, grid, dim3(WAVES * WAVE), 0,
+                       stream, keys, rows, is_new, master, shadow, s1, s2, n,
+                       V, D, tiles, seed, key_mul, key_add, scale);
+  else
+    hipLaunchKernelGGL(init_rows_kernel<1>, grid, dim3(WAVES * WAVE), 0,
+                       stream, keys, rows, is_new, master, shadow, s1, s2, n,
+                       V, D, tiles, seed, key_mul, key_add, scale);
+}

@@ -60,6 +60,17 @@ contributions in the order an unsharded table would, so the shards end
 bit-identical to the unsharded table. One device->host copy per request
 is unavoidable: the message sizes are the shard counts (``starts``).
 ``ShardedEmbeddingTable`` runs the same routing over local shards.
+
+Hashed tables. ``HashedEmbeddingTable`` takes ARBITRARY int64 keys (64-bit
+feature hashes, raw categorical ids of an open vocabulary) instead of row
+numbers in ``[0, V)`` and gives a key its row on first use — TF's
+``MutableHashTable`` / dynamic embedding variable. A device-resident hash
+index (``ops.HashIndex``, ``csrc/hash.hip``) translates keys to rows and
+every request then runs the row kernels above unchanged, so the server, the
+client and the wire format serve it as they serve an ``EmbeddingTable``; a
+new row's initial value is a pure function of (seed, key, column), so
+``HashedEmbeddingTable.shard_of`` shards (homes ``[ranks]``, ``rows={name:
+ops.HASH_KEY_SPACE}``, strategy "mod") equal the unsharded table key for key.
 """
 
 import threading
@@ -460,6 +471,228 @@ class ShardedEmbeddingTable(object):
                                  % (k, sd[k], getattr(self, k)))
         for t, shard_sd in zip(self.shards, sd["shards"]):
             t.load_state_dict(shard_sd)
+
+
+class HashedEmbeddingTable(object):
+    """A PS-resident table addressed by arbitrary int64 KEYS: a key gets the
+    next free row the first time a request names it (``ops.HashIndex``,
+    insert on first use), up to ``capacity`` rows.
+
+    Optimizers, hyper-parameters, ``step`` semantics and the signatures of
+    pull / push / pull_pooled / push_pooled are ``EmbeddingTable``'s, so a
+    stock ``SparsePSServer`` serves it. Every request translates its keys
+    to rows and runs the existing row op on them, under ONE hold of the
+    table's lock; a key without a row (row -1) is ignored by a push and
+    reads as a zero row. Pushes always take the fused sparse-apply path.
+
+    * Keys: every int64 except ``ops.HASH_EMPTY`` (INT64_MIN), which is
+      treated as absent and never inserted.
+    * Initial rows: column c of the row of key k is
+      ``ops.hash_init_rows``'s pure function of (seed, k, c) — uniform in
+      [0, dim**-0.5) like ``EmbeddingTable`` — whatever the insertion
+      order, capacity or sharding; the optimizer state of a new row is 0.
+    * ``insert_on_pull`` (default True, training): a pull of a first-seen
+      key inserts it and returns its real initial row, so the gradient
+      pushed back trains from it. False (serving): pulls never insert —
+      a row pull is the one-launch ``ops.hash_gather`` — and unknown keys
+      read as zero rows.
+    * A full table: a new key gets no row (its pushes are dropped, its
+      pulls read zeros) and ``stats()["dropped"]`` counts it, once per
+      request that names it; ``reserve`` makes room. There is no eviction
+      and no automatic growth.
+    * Sharding: ``shard_of`` shards take keys in ``[0,
+      ops.HASH_KEY_SPACE)`` = [0, 2**62) and the "mod" strategy only
+      (``SparseWorkerClient(table_homes={name: [ranks]}, rows={name:
+      ops.HASH_KEY_SPACE})``); an unsharded table takes the full key range.
+    * ``SparseWorkerClient(coalesce=True)`` works as is:
+      ``ops.coalesce_ids`` never looks at the id range."""
+
+    _HPARAMS = EmbeddingTable._HPARAMS
+    _STATE = EmbeddingTable._STATE
+    _push_fused = EmbeddingTable._push_fused    # same fields, same applies
+
+    def __init__(self, name, dim, capacity, device="cpu", lr=0.01, seed=0,
+                 optimizer="sgd", insert_on_pull=True, key_mul=1, key_add=0,
+                 **hparams):
+        """key_mul / key_add (``shard_of`` sets them): local key k stands
+        for the global key k * key_mul + key_add in the initialiser."""
+        if optimizer not in self._HPARAMS:
+            raise ValueError("unknown sparse optimizer %r (have %s)"
+                             % (optimizer, sorted(self._HPARAMS)))
+        hp = dict(self._HPARAMS[optimizer])
+        for k, v in hparams.items():
+            if k not in hp:
+                raise ValueError("optimizer %r has no hyper-parameter %r"
+                                 % (optimizer, k))
+            hp[k] = v
+        self.name = name
+        self.dim = dim
+        self.lr = lr
+        self.seed = int(seed)
+        self.key_mul, self.key_add = int(key_mul), int(key_add)
+        self.optimizer = optimizer
+        self.hparams = hp
+        self.insert_on_pull = bool(insert_on_pull)
+        self.step = 0
+        self.device = torch.device(device)
+        self.index = ops.HashIndex(capacity, self.device)
+        names = self._STATE[optimizer]
+        if optimizer == "sgd" and hp["momentum"]:
+            names = ("momentum_buf",)
+        self._state_names = names
+        self._alloc(self.index.capacity)
+        self.lock = threading.Lock()
+
+    @property
+    def capacity(self):
+        return self.index.capacity
+
+    def _alloc(self, capacity, old=None):
+        """Storage for ``capacity`` rows; the rows of ``old`` (master,
+        shadow, state) are copied in."""
+        def grown(t, dtype):
+            new = torch.zeros(capacity, self.dim, dtype=dtype,
+                              device=self.device)
+            if t is not None:
+                new[:t.shape[0]] = t
+            return new
+        om, osd, ost = old if old is not None else (None, None, {})
+        self.master = grown(om, torch.float32)
+        self.shadow = grown(osd, torch.bfloat16)
+        self.state = {k: grown(ost.get(k), torch.float32)
+                      for k in self._state_names}
+
+    @classmethod
+    def shard_of(cls, name, dim, shard, num_shards, capacity, **kw):
+        """Shard ``shard`` of the hashed table ``name`` split over
+        ``num_shards`` by ``key % num_shards`` ("mod", the only strategy):
+        its local key l stands for the global key l * num_shards + shard,
+        which is what the row initialiser sees, so the shards hold, key
+        for key, the rows of ``HashedEmbeddingTable(name, dim, ..., **kw)``.
+        ``capacity`` is this shard's own. Global keys lie in
+        [0, ops.HASH_KEY_SPACE)."""
+        if not 1 <= num_shards <= 64 or not 0 <= shard < num_shards:
+            raise ValueError("need 1 <= num_shards <= 64 and 0 <= shard < "
+                             "num_shards, got shard %r of %r"
+                             % (shard, num_shards))
+        return cls(name, dim, capacity, key_mul=num_shards, key_add=shard,
+                   **kw)
+
+    def _rows(self, keys, insert):
+        """Key -> row translation of one request (lock held): with
+        ``insert`` absent keys get rows, initialised in the same breath."""
+        keys = keys.to(self.device)
+        if not insert:
+            return ops.hash_find(self.index, keys)
+        rows, is_new = ops.hash_find_or_insert(self.index, keys)
+        ops.hash_init_new_rows(keys, rows, is_new, self.master, self.shadow,
+                               list(self.state.values()), self.seed,
+                               self.key_mul, self.key_add)
+        return rows
+
+    def pull(self, ids):
+        """bf16 rows for the keys ``ids``; zero rows for keys without one."""
+        with self.lock:
+            if not self.insert_on_pull:
+                return ops.hash_gather(self.index, self.shadow,
+                                       ids.to(self.device))
+            rows = self._rows(ids, True)
+            if self.device.type == "cpu":   # index_select cannot take -1
+                return ops._rows_or_zero(self.shadow, rows)
+            return ops.embedding_gather(self.shadow, rows)
+
+    def push(self, ids, grads, lr=None):
+        """Sparse apply of one push to the rows of the keys ``ids``
+        (inserted on first use); duplicates sum, ``step`` advances once."""
+        lr = self.lr if lr is None else lr
+        with self.lock:
+            self._push_fused(self._rows(ids, True), grads, lr)
+
+    def pull_pooled(self, ids, offsets, weights=None, combiner="sum",
+                    out_dtype=None):
+        """``EmbeddingTable.pull_pooled`` over keys; a key without a row
+        contributes nothing but still counts in a mean's weight sum."""
+        with self.lock:
+            rows = self._rows(ids, self.insert_on_pull)
+            return ops.embedding_bag(self.shadow, rows, offsets,
+                                     weights=weights, combiner=combiner,
+                                     out_dtype=out_dtype)
+
+    def push_pooled(self, ids, offsets, bag_grads, weights=None,
+                    combiner="sum", lr=None):
+        """``EmbeddingTable.push_pooled`` over keys (inserted on first
+        use)."""
+        lr = self.lr if lr is None else lr
+        with self.lock:
+            self._push_fused(self._rows(ids, True), bag_grads, lr,
+                             offsets=offsets, weights=weights,
+                             combiner=combiner)
+
+    def stats(self):
+        """{"size", "dropped", "capacity"} — THE place that syncs: the two
+        counters live on the device and nothing else reads them."""
+        with self.lock:
+            size, dropped = torch.cat(
+                [self.index.size, self.index.dropped]).tolist()
+            return {"size": size, "dropped": dropped,
+                    "capacity": self.index.capacity}
+
+    def reserve(self, capacity):
+        """Grow to ``capacity`` rows (explicit; nothing grows by itself):
+        larger master, shadow and state with the old rows copied, a larger
+        slot array, and ``ops.hash_rebuild``. The key -> row mapping and
+        every row are unchanged; no host sync."""
+        with self.lock:
+            if capacity < self.index.capacity:
+                raise ValueError("reserve(%d): table %r already has capacity "
+                                 "%d" % (capacity, self.name,
+                                         self.index.capacity))
+            if capacity == self.index.capacity:
+                return
+            self.index.reserve(capacity)
+            self._alloc(capacity, (self.master, self.shadow, self.state))
+
+    def state_dict(self):
+        """keys = row_keys[:size], the first ``size`` rows of master and
+        optimizer state, step and seed (CPU copies); row r belongs to
+        keys[r]."""
+        with self.lock:
+            n = int(self.index.size)
+            return {
+                "optimizer": self.optimizer,
+                "keys": self.index.row_keys[:n].cpu().clone(),
+                "master": self.master[:n].cpu().clone(),
+                "state": {k: v[:n].cpu().clone()
+                          for k, v in self.state.items()},
+                "step": self.step,
+                "seed": self.seed,
+            }
+
+    def load_state_dict(self, sd):
+        """Load into this table (any capacity >= the checkpoint's size):
+        the keys keep their rows, index and shadow are rebuilt, and the
+        table takes the checkpoint's seed — it then trains on exactly as
+        the saved one would have."""
+        if sd["optimizer"] != self.optimizer:
+            raise ValueError("checkpoint is for optimizer %r, table uses %r"
+                             % (sd["optimizer"], self.optimizer))
+        if set(sd["state"]) != set(self.state):
+            raise ValueError("checkpoint state %s does not match table "
+                             "state %s" % (sorted(sd["state"]),
+                                           sorted(self.state)))
+        n = sd["keys"].numel()
+        if n > self.index.capacity:
+            raise ValueError("checkpoint holds %d keys, table %r has "
+                             "capacity %d" % (n, self.name,
+                                              self.index.capacity))
+        with self.lock:
+            self.index.assign(sd["keys"])
+            self.master[:n].copy_(sd["master"])
+            for k, v in sd["state"].items():
+                self.state[k][:n].copy_(v)
+            self.shadow[:n].copy_(self.master[:n].to(torch.bfloat16))
+            self.step = int(sd["step"])
+            self.seed = int(sd["seed"])
 
 
 def make_sparse_pair_groups(ps_ranks, worker_ranks):
