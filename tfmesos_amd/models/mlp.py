@@ -5,8 +5,8 @@ Same architecture/hyperparameters as the reference benchmark workload
 stddev 1/sqrt(784), hidden 100, batch 100, lr 0.01). Forward AND backward
 are written explicitly against ``tfmesos_amd.ops`` (bf16 MFMA GEMM +
 fused softmax-xent + fused relu-bwd on GPU) — no autograd in the hot
-path, so the step is a short fixed kernel sequence (3 kernels at the
-benchmark geometry: fwd split-K stripes, their reduce, and the fused
+path, so the step is a short fixed kernel sequence (2 kernels at the
+benchmark geometry: the one-launch split-K forward and the fused
 head+tail; GraphedStep can capture it and self-tunes graph-vs-eager).
 """
 
@@ -77,7 +77,8 @@ class MnistMLP(object):
         hid_w, hid_b = p("hid_w"), p("hid_b")
         sm_w, sm_b = p("sm_w"), p("sm_b")
 
-        # fwd hidden layer: split-K GEMM + bias + relu
+        # fwd hidden layer: split-K GEMM + bias + relu (one launch up
+        # to 128x128 outputs: the K slices are one workgroup's waves)
         h = ops.gemm_bias_act(x, hid_w, hid_b, act="relu")       # [B,H]
         small = B <= 128 and self.hidden <= 128 and self.classes <= 16
         # from 32 tiles up (where gemm_bias_act runs dW1 on the
@@ -89,8 +90,8 @@ class MnistMLP(object):
             # head + dW1 tail in ONE kernel (csrc/gemm.hip
             # mlp_head_tail_kernel): each block of the dW1 GEMM
             # recomputes the logits/softmax/dh slice it consumes, so
-            # the head launch, dh and dlogits disappear — 3 launches
-            # (fwd GEMM stripes, its reduce, head+tail) + the apply
+            # the head launch, dh and dlogits disappear — 2 launches
+            # (fwd GEMM, head+tail) + the apply
             return ops.mlp_head_tail_grads(
                 x, h, sm_w, sm_b, y, g("hid_w"), g("hid_b"),
                 g("sm_w"), g("sm_b"))
@@ -100,15 +101,15 @@ class MnistMLP(object):
             # (csrc/softmax_xent.hip): logits GEMM + softmax + loss +
             # dlogits + relu-masked dh + dW2/db2. At this size each
             # launch is ~4-7 us of execution floor, so kernel COUNT is
-            # the step time: 5 launches total (fwd GEMM stripes, its
-            # reduce, head, dW1, apply). Two measured dead ends kept
+            # the step time: 4 launches total (fwd GEMM, head, dW1,
+            # apply). Two measured dead ends kept
             # out: forking dW2 to a side stream (event edges cost more
             # than the GEMM they overlap), and consuming the fwd
             # split-K stripes directly in the head
             # (ops.mlp_fwd_head_fused — a SINGLE workgroup pulling
             # 360 KB of stripes from 8 XCDs' L2s took ~36 us; one-WG
-            # consumers must read tiny inputs, so the many-WG reduce
-            # kernel stays).
+            # consumers must read tiny inputs. The forward now sums
+            # its K slices inside each workgroup instead).
             loss, dlogits, dh = ops.mlp_head_fused(
                 h, sm_w, sm_b, y, dw2=g("sm_w"), db2=g("sm_b"))
             ops.gemm_bias_act(x, dh, trans_a=True, out=g("hid_w"),
@@ -138,10 +139,10 @@ class MnistMLP(object):
 
     def fwd_bwd_apply(self, trainer, x, y, lr):
         """One fused replica step (world==1 fast path): fwd GEMM
-        (stripes + reduce, which also snapshots the 2 KB classifier
+        (one launch, which also snapshots the 2 KB classifier
         shadow) -> ONE head+tail kernel that recomputes the
         classifier head per wave, computes dW1 and applies SGD to all
-        four params (ops.mlp_head_tail_sgd). 3 kernels/step; same
+        four params (ops.mlp_head_tail_sgd). 2 kernels/step; same
         math, bit for bit, as the previous head kernel + tail kernel
         sequence (ops.mlp_head_fused -> ops.mlp_tail_sgd), which
         TFA_MLP_HEADTAIL=0 or a shape outside the fused kernel's
@@ -152,8 +153,8 @@ class MnistMLP(object):
         p = lambda n: st.view(n, bf16=True)
         g = trainer.grad_view
         if self._headtail_ok(x):
-            # the fwd GEMM's stripe reduce snapshots W2/b2 on its way,
-            # so the fused kernel can apply them without a ticket
+            # the fwd GEMM's launch snapshots W2/b2 on its way, so
+            # the fused kernel can apply them without a ticket
             h, snap = ops.mlp_fwd_snap(x, p("hid_w"), p("hid_b"),
                                        p("sm_w"), p("sm_b"))
             loss = ops.mlp_head_tail_sgd(

@@ -138,8 +138,16 @@ def fused_adagrad(param, grad, accum, lr, eps=1e-10, weight_decay=0.0,
 
 # --------------------------------------------------------------------- gemm
 
+GEMM_ROUTES = {"auto": 0, "stripes": 1, "fwd1": 2}
+# gemm_fwd1_kernel geometries kept for measurement (tile, "s": strided B)
+GEMM_FWD1_VARIANTS = {None: -1, "16x16": 0, "16x32": 1, "32x16": 2,
+                      "32x32": 3, "16x16s": 4, "16x32s": 5, "32x16s": 6,
+                      "32x32s": 7}
+
+
 def gemm_bias_act(a, b, bias=None, act="none", trans_a=False, trans_b=False,
-                  out=None, aux=None, colsum_out=None):
+                  out=None, aux=None, colsum_out=None, route="auto",
+                  fwd1_variant=None):
     """C = act(op(A) @ op(B) + bias), bf16 in, fp32 accumulate.
 
     Output dtype: bf16 by default; pass ``out`` (bf16 or fp32) to write
@@ -153,8 +161,18 @@ def gemm_bias_act(a, b, bias=None, act="none", trans_a=False, trans_b=False,
 
     GPU: hand-written MFMA kernel (csrc/gemm.hip) with split-K for deep
     skinny shapes. CPU: torch reference in fp32.
+
+    ``route`` picks the kernels of a K-sliced plain forward (GPU only;
+    the results are bit-identical): ``"auto"`` (one launch for outputs
+    up to 128x128, unless TFA_GEMM_FWD1=0), ``"stripes"`` (always
+    split-K stripes + reduce) or ``"fwd1"`` (always the one-launch
+    kernel; raises unless the call is nn, act none/relu, without
+    aux/colsum, and slices K 2..16 ways). ``fwd1_variant`` selects one
+    of GEMM_FWD1_VARIANTS instead of the shipped geometry.
     """
     act_code = {"none": 0, "relu": 1, "relu_bwd": 2, "sub": 3}[act]
+    route_code = GEMM_ROUTES[route]
+    variant_code = GEMM_FWD1_VARIANTS[fwd1_variant]
     if a.is_cuda:
         empty = torch.empty(0, device=a.device)
         ebias = bias if bias is not None else empty
@@ -165,6 +183,10 @@ def gemm_bias_act(a, b, bias=None, act="none", trans_a=False, trans_b=False,
                 (a.shape[1] if trans_a else a.shape[0],
                  b.shape[0] if trans_b else b.shape[1]),
                 device=a.device, dtype=a.dtype)
+        if route_code or variant_code >= 0:
+            return _ext().gemm_bias_act_route(
+                a, b, ebias, act_code, bool(trans_a), bool(trans_b), out,
+                eaux, ecs, route_code, variant_code)
         return _ext().gemm_bias_act_out(a, b, ebias, act_code,
                                         bool(trans_a), bool(trans_b), out,
                                         eaux, ecs)
@@ -1586,12 +1608,12 @@ def mlp_head_tail_grads(x, h, w2, b2, y, dw1, db1, dw2, db2):
 
 def mlp_fwd_snap(x, w1, b1, w2_s, b2_s):
     """mnist fwd hidden layer h = relu(x @ w1 + b1) (same kernels and
-    bits as gemm_bias_act) whose split-K stripe reduce ALSO copies the
-    2 KB classifier shadow (w2_s, b2_s) into a per-device snapshot
-    buffer. Returns (h, snap) for mlp_head_tail_sgd(snap=...): reading
+    bits as gemm_bias_act) whose launch (the one-launch forward, or the
+    split-K stripe reduce) ALSO copies the 2 KB classifier shadow
+    (w2_s, b2_s) into a per-device snapshot buffer. Returns (h, snap) for mlp_head_tail_sgd(snap=...): reading
     the snapshot instead of the live shadow lets it apply W2/b2 without
     the arrival ticket (~5 us). snap is None where the GEMM runs a path
-    without that reduce kernel, and on CPU."""
+    that takes no snapshot, and on CPU."""
     if x.is_cuda:
         h, snap = _ext().mlp_fwd_snap(x, w1, b1, w2_s, b2_s)
         return h, (snap if snap.numel() else None)

@@ -32,7 +32,8 @@ struct SmallSgdArgs {
   int n2w, n2b;
 };
 
-// optional side job of the small split-K stripe reduce (gemm.hip): copy
+// optional side job of the one-launch forward GEMM and of the small
+// split-K stripe reduce (gemm.hip): copy
 // two small bf16 ranges into dst[0..n0) and dst[off1..off1+n1) — the
 // mnist step snapshots the classifier shadow there, one launch ahead
 // of the fused head+tail kernel that reads it

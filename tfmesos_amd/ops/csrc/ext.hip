@@ -42,6 +42,9 @@ void launch_gemm_stripes(const bf16_t*, const bf16_t*, float*, int, int,
 void launch_gemm_small(const bf16_t*, const bf16_t*, const void*, bool,
                        void*, bool, int, void*, bool, int, int, int, int,
                        int, int, bool, const SmallSgdArgs*, hipStream_t);
+void launch_gemm_fwd1(const bf16_t*, const bf16_t*, const void*, bool, void*,
+                      bool, int, int, int, int, int, int, int, int, int, int,
+                      int, int, const SnapArgs*, bool*, hipStream_t);
 void launch_mlp_head_tail(const bf16_t*, const HeadTailArgs*, void*, void*,
                           bool, int, int, int, const SmallSgdArgs*,
                           hipStream_t);
@@ -242,13 +245,21 @@ float* splitk_ws(const torch::Device& dev, long n, long ntiles, int** cnt) {
   return w.data_ptr<float>();
 }
 
-// snap / snap_taken: optional side copy riding the small stripe reduce
-// (see SnapArgs); *snap_taken stays false on every other kernel path
+// snap / snap_taken: optional side copy riding the one-launch forward
+// or the small stripe reduce (see SnapArgs); *snap_taken stays false on
+// every other kernel path.
+// route: which kernels a K-sliced nn forward runs on — 0 auto, 1 always
+// split-K stripes + reduce, 2 always the one-launch gemm_fwd1_kernel
+// (raises when the call is outside that kernel's limits). variant: see
+// launch_gemm_fwd1 (< 0: the shipped geometry).
 torch::Tensor gemm_bias_act_impl(torch::Tensor a, torch::Tensor b,
                                  torch::Tensor bias, long act, bool trans_a,
                                  bool trans_b, torch::Tensor out,
                                  torch::Tensor aux, torch::Tensor colsum_out,
-                                 const SnapArgs* snap, bool* snap_taken) {
+                                 const SnapArgs* snap, bool* snap_taken,
+                                 long route = 0, long variant = -1) {
+  TORCH_CHECK(route >= 0 && route <= 2 && variant >= -1 && variant <= 7,
+              "gemm: bad route / variant");
   TORCH_CHECK(a.is_cuda() && b.is_cuda(), "gemm: tensors must be on GPU");
   TORCH_CHECK(a.scalar_type() == torch::kBFloat16 &&
               b.scalar_type() == torch::kBFloat16, "gemm: bf16 inputs only");
@@ -355,13 +366,40 @@ torch::Tensor gemm_bias_act_impl(torch::Tensor a, torch::Tensor b,
     if (want > 1) {
       kc = ((Ka + want - 1) / want + 31) / 32 * 32;
       nslice = (Ka + kc - 1) / kc;
-      if (nslice > 1)
-        ws = splitk_ws(a.device(),
-                       (long)M * N * nslice +
-                           (colsum_p != nullptr ? (long)nslice * N : 0),
-                       (long)nx * ny, &cnt);
     }
   }
+  // one-launch forward: the K slices become the waves of one workgroup
+  // (gemm_fwd1_kernel, bit-identical to stripes + reduce, so the gate
+  // is a speed decision only: outputs up to 128x128, where the stripes
+  // grid is at most 2x2 tiles and its reduce a second dispatch floor).
+  // TFA_GEMM_FWD1=0 restores the two-kernel path for A/B runs.
+  static int fwd1_on = -1;
+  if (fwd1_on < 0) {
+    const char* e = getenv("TFA_GEMM_FWD1");
+    fwd1_on = e ? (atoi(e) != 0) : 1;
+  }
+  const bool fwd1_fits = !trans_a && !trans_b && act <= 1 &&
+                         aux_p == nullptr && colsum_p == nullptr &&
+                         nslice > 1 && nslice <= 16;
+  TORCH_CHECK(route != 2 || fwd1_fits,
+              "gemm: one-launch route needs nn, act none/relu, no aux, no "
+              "colsum and 2..16 K slices (got ", nslice, ")");
+  if (route == 2 ||
+      (route == 0 && fwd1_on && fwd1_fits && M <= 128 && N <= 128)) {
+    launch_gemm_fwd1((const bf16_t*)a.data_ptr(),
+                     (const bf16_t*)b.data_ptr(), bias_p, bias_bf16,
+                     out.data_ptr(), out_f32, act == 1 ? 1 : 0, kc, nslice,
+                     M, N, Ka, a.size(1), b.size(1), N,
+                     vec_level(a.data_ptr(), a.size(1)),
+                     vec_level(b.data_ptr(), b.size(1)), (int)variant, snap,
+                     snap_taken, cur_stream());
+    return out;
+  }
+  if (nslice > 1)
+    ws = splitk_ws(a.device(),
+                   (long)M * N * nslice +
+                       (colsum_p != nullptr ? (long)nslice * N : 0),
+                   (long)nx * ny, &cnt);
   launch_gemm((const bf16_t*)a.data_ptr(), (const bf16_t*)b.data_ptr(),
               bias_p, bias_bf16, out.data_ptr(), out_f32, aux_p, colsum_p,
               ws, cnt, kc, nslice, M, N, Ka, a.size(1), b.size(1), N,
@@ -380,12 +418,24 @@ torch::Tensor gemm_bias_act_out(torch::Tensor a, torch::Tensor b,
                             colsum_out, nullptr, nullptr);
 }
 
-// mnist fwd hidden layer h = relu(x @ w1 + b1) whose stripe reduce also
-// snapshots the classifier shadow (w2s [H,C], b2s [C]) for the fused
-// head+tail kernel that follows. Returns (h, snap): snap is the
-// per-device snapshot buffer (w2 at 0, b2 at 2048), or EMPTY when the
-// GEMM took a kernel path without the small stripe reduce — the caller
-// then uses the live shadow and the arrival ticket.
+// gemm_bias_act_out with an explicit route for K-sliced nn forwards
+// (see gemm_bias_act_impl), so both routes run inside one process
+torch::Tensor gemm_bias_act_route(torch::Tensor a, torch::Tensor b,
+                                  torch::Tensor bias, long act, bool trans_a,
+                                  bool trans_b, torch::Tensor out,
+                                  torch::Tensor aux, torch::Tensor colsum_out,
+                                  long route, long variant) {
+  return gemm_bias_act_impl(a, b, bias, act, trans_a, trans_b, out, aux,
+                            colsum_out, nullptr, nullptr, route, variant);
+}
+
+// mnist fwd hidden layer h = relu(x @ w1 + b1) whose launch (the
+// one-launch forward, or the small stripe reduce) also snapshots the
+// classifier shadow (w2s [H,C], b2s [C]) for the fused head+tail kernel
+// that follows. Returns (h, snap): snap is the per-device snapshot
+// buffer (w2 at 0, b2 at 2048), or EMPTY when the GEMM took a kernel
+// path that takes no snapshot — the caller then uses the live shadow
+// and the arrival ticket.
 constexpr int kSnapB2Off = 2048;
 std::vector<torch::Tensor> mlp_fwd_snap(torch::Tensor x, torch::Tensor w1,
                                         torch::Tensor b1, torch::Tensor w2s,
@@ -2080,6 +2130,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bf16_out"), py::arg("lr"), py::arg("eps") = 1e-10,
         py::arg("weight_decay") = 0.0, py::arg("grad_scale") = 1.0);
   m.def("gemm_bias_act", &gemm_bias_act, "bf16 MFMA GEMM + bias + act");
+  m.def("gemm_bias_act_route", &gemm_bias_act_route);
   m.def("gemm_bias_act_out", &gemm_bias_act_out,
         "bf16 MFMA GEMM + fused epilogue (bias/act/relu_bwd/colsum) into "
         "out (bf16 or fp32), split-K for deep skinny shapes");

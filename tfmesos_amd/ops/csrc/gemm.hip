@@ -18,6 +18,10 @@
 //    the acquire fence — DETERMINISTIC and memory-model-clean (an
 //    in-kernel last-arriver tail measured 3x slower: its uncached
 //    per-element loads serialize).
+//  * one-launch split-K for outputs up to 128x128 (gemm_fwd1_kernel):
+//    the K slices of a tile are the waves of ONE workgroup and meet in
+//    LDS — same sums in the same order as stripes + reduce, without
+//    the workspace round trip and the second dispatch.
 //  * vectorized LDS staging: b128 loads when the operand's leading dim
 //    and base allow, b32 otherwise; both [X,K] and [K,X] storage orders
 //    have contiguous global access patterns.
@@ -403,6 +407,234 @@ void splitk_reduce_kernel(const float* __restrict__ ws, const void* __restrict__
   }
 }
 
+// ------------------------------------------------ one-launch split-K fwd
+//
+// C = act(A @ B + bias) for small outputs whose K has to be sliced (the
+// mnist fwd 100x100x784): the K slices of one output tile are the WAVES
+// of one workgroup instead of separate workgroups, and the fp32 partials
+// meet in LDS instead of a global stripe workspace. One launch, one
+// barrier, no workspace, no counters, no fences, no atomics. Wave z owns
+// k in [z*kc, min((z+1)*kc, K)) with the kc / nslice the binding computes
+// for the stripes path, chains the same 16x16x32 MFMAs over its k-steps
+// in ascending order with gemm_kernel's operand placement, and the block
+// then sums the partials z = 0..nslice-1 in that order before the
+// bias/relu/cast — per element exactly gemm_kernel<SK> followed by the
+// stripe reduce, so the two routes agree bit for bit.
+//
+// Loads: every global load of up to F1_KS k-steps (the whole slice at
+// kc <= 96) is issued before the first wait, so a wave is one memory
+// round trip deep. A fragments come straight from global (one b128 per
+// lane when rows are 16B-aligned). B ([K,N], 8 k per lane) is loaded
+// row-wise as dword-aligned b128 chunks and transposed through a
+// wave-private k-major LDS image read back with ds_read_b64_tr_b16
+// (the per-wave DS pipe is in order: no barrier), or loaded strided
+// straight into the fragment when B rows are not dword-aligned. A B
+// chunk that straddles N is read as the row's last whole chunk and
+// shifted at commit time; unaligned operands take guarded element
+// loads. Positions beyond M, N, K are zero-filled, never read.
+//
+// The wave's fp32 partial overlays its own (dead) B image; every LDS
+// access in the kernel goes through __bf16 vector types, so the
+// overlay involves no differently-typed views of the same bytes.
+// sj: the W2/b2 snapshot side job (as in the small stripe reduce), done
+// by the last (ragged) block; its loads are issued first and stored before
+// the barrier, so the copy rides under the GEMM's own round trip.
+typedef bf16x8 __attribute__((aligned(4))) bf16x8_a4;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+constexpr int F1_KS = 3;   // k-steps in flight per wave
+// shipped tile (launch_gemm_fwd1's variant code); measurements of all
+// four are in docs/KERNELS.md
+constexpr int kFwd1Tile = 0;
+
+// elements P[off + j*stride] for j < nvalid, zeros beyond (never read):
+// the guarded path of operands whose rows allow no vector access
+DEVINL bf16x8 f1_load8(const __bf16* __restrict__ P, long off, long stride,
+                       int nvalid) {
+  bf16x8 v = {};
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (j < nvalid) v[j] = P[off + j * stride];
+  return v;
+}
+
+template <int TM, int TN>
+struct Fwd1Geo {
+  static constexpr int FM = TM / 16, FN = TN / 16;
+  static constexpr int BP = TN + 8;          // B image row pitch, elems
+  static constexpr int IMG_BYTES = BK * BP * 2;
+  static constexpr int PART_BYTES = TM * TN * 4;
+  static constexpr int WAVE_BYTES =
+      IMG_BYTES > PART_BYTES ? IMG_BYTES : PART_BYTES;
+};
+
+// VA: A rows 16B-aligned and K % 8 == 0 (a k chunk is whole or absent).
+// VB: B rows dword-aligned, N even and >= 8.
+template <int TM, int TN, bool VA, bool VB>
+__global__ __launch_bounds__(1024)
+void gemm_fwd1_kernel(const __bf16* __restrict__ A,
+                      const __bf16* __restrict__ B,
+                      const void* __restrict__ bias, bool bias_bf16,
+                      void* __restrict__ Cout, bool out_f32, int relu,
+                      int M, int N, int K, int lda, int ldb, int ldc, int kc,
+                      SnapJob sj) {
+  using G = Fwd1Geo<TM, TN>;
+  constexpr int FM = G::FM, FN = G::FN, BP = G::BP;
+  extern __shared__ __align__(16) __bf16 f1_smem[];
+  const int t = threadIdx.x;
+  const int nth = blockDim.x;
+  const int lane = t & 63;
+  const int z = t >> 6;                 // K slice of this wave
+  const int nslice = nth >> 6;
+  const int m0 = blockIdx.y * TM;
+  const int n0 = blockIdx.x * TN;
+  const int ks = z * kc;
+  const int ke = min(ks + kc, K);
+  const int kfrag = (lane >> 4) * 8;
+  __bf16* img = f1_smem + z * (G::WAVE_BYTES / 2);
+
+  // snapshot side job: loads first, stores before the barrier
+  const bool snapper = sj.dst != nullptr && blockIdx.x == gridDim.x - 1 &&
+                       blockIdx.y == gridDim.y - 1;
+  const int sn = sj.n0 + sj.n1;
+  __bf16 sv[2] = {};
+  if (snapper) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int j = t + u * nth;
+      if (j < sn) sv[u] = j < sj.n0 ? sj.s0[j] : sj.s1[j - sj.n0];
+    }
+  }
+
+  // this thread's first epilogue element (see the combine loop): its
+  // bias is fetched now, not after the barrier
+  float bv = 0.f;
+  if (bias != nullptr && t < TM * TN) {
+    const int col = n0 + ((t >> 8) % FN) * 16 + ((t >> 2) & 15);
+    if (col < N)
+      bv = bias_bf16 ? (float)((const __bf16*)bias)[col]
+                     : ((const float*)bias)[col];
+  }
+
+  f32x4 acc[FM][FN] = {};
+  for (int kb = ks; kb < ke; kb += F1_KS * BK) {
+    bf16x8 ra[F1_KS][FM];
+    bf16x8 rb[F1_KS][FN];
+#pragma unroll
+    for (int s = 0; s < F1_KS; ++s) {
+      const int k0 = kb + s * BK;
+#pragma unroll
+      for (int fm = 0; fm < FM; ++fm) {
+        ra[s][fm] = bf16x8{};
+        const int row = m0 + fm * 16 + (lane & 15);
+        const int gk = k0 + kfrag;
+        if (k0 < ke && row < M && gk < K) {
+          const long off = (long)row * lda + gk;
+          if (VA) ra[s][fm] = *(const bf16x8*)(A + off);
+          else ra[s][fm] = f1_load8(A, off, 1, K - gk);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < FN; ++u) {
+        rb[s][u] = bf16x8{};
+        if (VB) {
+          // row-wise chunk u*64+lane of the [BK][TN] tile. A chunk that
+          // straddles N is read as the row's LAST whole chunk (in
+          // bounds, still dword-aligned) and shifted into place at
+          // commit time — one unconditional b128 either way
+          const int c = u * 64 + lane;
+          const int gk = k0 + c / (TN / 8);
+          const int gn = n0 + (c % (TN / 8)) * 8;
+          if (k0 < ke && gk < K && gn < N)
+            rb[s][u] =
+                *(const bf16x8_a4*)(B + (long)gk * ldb + min(gn, N - 8));
+        } else {
+          // fragment u straight from global, one element per load
+          const int col = n0 + u * 16 + (lane & 15);
+          const int gk = k0 + kfrag;
+          if (k0 < ke && col < N && gk < K)
+            rb[s][u] = f1_load8(B, (long)gk * ldb + col, ldb, K - gk);
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < F1_KS; ++s) {
+      if (kb + s * BK >= ke) break;
+      bf16x8 bf[FN];
+      if (VB) {
+#pragma unroll
+        for (int u = 0; u < FN; ++u) {
+          const int c = u * 64 + lane;
+          const int gn = n0 + (c % (TN / 8)) * 8;
+          // dwords the chunk was read early by (N even); live columns
+          // move down, zeros come in above them
+          const int sh = (gn - min(gn, N - 8)) >> 1;
+          u32x4 d = __builtin_bit_cast(u32x4, rb[s][u]);
+          if (sh & 1) d = u32x4{d[1], d[2], d[3], 0u};
+          if (sh & 2) d = u32x4{d[2], d[3], 0u, 0u};
+          *(bf16x8*)&img[(c / (TN / 8)) * BP + (c % (TN / 8)) * 8] =
+              __builtin_bit_cast(bf16x8, d);
+        }
+#pragma unroll
+        for (int fn = 0; fn < FN; ++fn) {
+          const int a = (kfrag + ((lane & 15) >> 2)) * BP + fn * 16 +
+                        4 * (lane & 3);
+          bf16x4 f0 = tr_read(&img[a]);
+          bf16x4 f1 = tr_read(&img[a + 4 * BP]);
+          bf[fn] = __builtin_shufflevector(f0, f1, 0, 1, 2, 3, 4, 5, 6, 7);
+        }
+      } else {
+#pragma unroll
+        for (int fn = 0; fn < FN; ++fn) bf[fn] = rb[s][fn];
+      }
+#pragma unroll
+      for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < FN; ++fn)
+          acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              ra[s][fm], bf[fn], acc[fm][fn], 0, 0, 0);
+    }
+  }
+
+  // partial fragment f = fm*FN+fn of slice z: float (f*64 + lane)*4 + r
+#pragma unroll
+  for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+    for (int fn = 0; fn < FN; ++fn)
+      *(bf16x8*)&img[((fm * FN + fn) * 64 + lane) * 8] =
+          __builtin_bit_cast(bf16x8, acc[fm][fn]);
+
+  if (snapper) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int j = t + u * nth;
+      if (j < sn) sj.dst[j < sj.n0 ? j : sj.off1 + (j - sj.n0)] = sv[u];
+    }
+    for (int j = t + 2 * nth; j < sn; j += nth)
+      sj.dst[j < sj.n0 ? j : sj.off1 + (j - sj.n0)] =
+          j < sj.n0 ? sj.s0[j] : sj.s1[j - sj.n0];
+  }
+  __syncthreads();
+
+  for (int e = t; e < TM * TN; e += nth) {
+    const int r = e & 3, pl = (e >> 2) & 63, f = e >> 8;
+    const int col = n0 + (f % FN) * 16 + (pl & 15);
+    const int row = m0 + (f / FN) * 16 + (pl >> 4) * 4 + r;
+    if (row >= M || col >= N) continue;
+    float v = 0.f;
+    for (int z2 = 0; z2 < nslice; ++z2)
+      v += __builtin_bit_cast(
+          float, *(const bf16x2*)&f1_smem[z2 * (G::WAVE_BYTES / 2) + e * 2]);
+    if (bias != nullptr)
+      v += e == t ? bv
+                  : (bias_bf16 ? (float)((const __bf16*)bias)[col]
+                               : ((const float*)bias)[col]);
+    if (relu) v = v > 0.f ? v : 0.f;
+    const long idx = (long)row * ldc + col;
+    if (out_f32) ((float*)Cout)[idx] = v;
+    else ((__bf16*)Cout)[idx] = (__bf16)v;
+  }
+}
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
@@ -787,7 +1019,8 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
 // snapshot of W2/b2 (the small stripe reduce, SnapJob), the kernel
 // reads the snapshot instead (ticket == null) and a fixed block
 // applies to the live shadow concurrently — no atomics at all. The
-// ticket stays for shapes whose fwd GEMM has no such reduce launch.
+// ticket stays for shapes whose fwd GEMM takes no snapshot. (The
+// one-launch forward, gemm_fwd1_kernel, takes it the same way.)
 // Unlike the rejected split-K last-arriver epilogue, the ticket's last
 // arriver reads NOTHING another block wrote in this launch — no stripe
 // pull, no acquire of foreign data, no L1-staleness hazard; the ticket
@@ -1292,6 +1525,50 @@ void launch_gemm(const bf16_t* A, const bf16_t* B, const void* bias,
 #undef DISP_BIAS
 #undef DISP_OUT
 #undef LAUNCH
+}
+
+// one-launch split-K forward (see gemm_fwd1_kernel). variant < 0: the
+// shipped geometry; else bits 0-1 pick the tile (0 16x16, 1 16x32,
+// 2 32x16, 3 32x32) and bit 2 forces the strided B load — kept for the
+// microbenchmark. Shape limits are checked by the binding.
+void launch_gemm_fwd1(const bf16_t* A, const bf16_t* B, const void* bias,
+                      bool bias_bf16, void* C, bool out_f32, int relu,
+                      int kc, int nslice, int M, int N, int K, int lda,
+                      int ldb, int ldc, int veca, int vecb, int variant,
+                      const SnapArgs* snap, bool* snap_taken,
+                      hipStream_t stream) {
+  SnapJob sj = {};
+  if (snap != nullptr) {
+    sj.s0 = (const __bf16*)snap->s0; sj.s1 = (const __bf16*)snap->s1;
+    sj.dst = (__bf16*)snap->dst;
+    sj.n0 = snap->n0; sj.n1 = snap->n1; sj.off1 = snap->off1;
+  }
+  if (snap_taken) *snap_taken = snap != nullptr;
+  if (variant < 0) variant = kFwd1Tile;
+  // A b128 per lane: 16B-aligned rows and no ragged k chunk; B dword-
+  // aligned row chunks: even pitch and an even number of live columns
+  const bool va = veca == 8 && K % 8 == 0;
+  const bool vb = vecb >= 2 && N % 2 == 0 && N >= 8 && !(variant & 4);
+  dim3 block(64 * nslice);
+#define F1V(TMv, TNv, VAv, VBv)                                             \
+  hipLaunchKernelGGL((gemm_fwd1_kernel<TMv, TNv, VAv, VBv>),                \
+                     dim3(ceil_div(N, TNv), ceil_div(M, TMv)), block,       \
+                     (nslice * (Fwd1Geo<TMv, TNv>::WAVE_BYTES)), stream,    \
+                     (const __bf16*)A, (const __bf16*)B, bias, bias_bf16,   \
+                     C, out_f32, relu, M, N, K, lda, ldb, ldc, kc, sj)
+#define F1(TMv, TNv)                                                        \
+  do { if (va) { if (vb) F1V(TMv, TNv, true, true);                         \
+                 else F1V(TMv, TNv, true, false); }                         \
+       else    { if (vb) F1V(TMv, TNv, false, true);                        \
+                 else F1V(TMv, TNv, false, false); } } while (0)
+  switch (variant & 3) {
+    case 0: F1(16, 16); break;
+    case 1: F1(16, 32); break;
+    case 2: F1(32, 16); break;
+    default: F1(32, 32); break;
+  }
+#undef F1
+#undef F1V
 }
 
 // split-K phase 1 ONLY: store the fp32 partial stripes and return —

@@ -51,9 +51,31 @@ def main():
     flat_g = torch.randn_like(flat)
     flat_bf = flat.to(torch.bfloat16)
 
+    def fwd(route, variant=None, a=x, w=hid_w, b=hid_b):
+        return lambda: ops.gemm_bias_act(a, w, b, act="relu", route=route,
+                                         fwd1_variant=variant)
+
     rows = [
-        ("fwd1 gemm+bias+relu [100x784]@[784x100] (split-K)",
+        ("fwd1 gemm+bias+relu [100x784]@[784x100] (auto)",
          lambda: ops.gemm_bias_act(x, hid_w, hid_b, act="relu")),
+        ("  route=stripes (split-K stripes + reduce)", fwd("stripes")),
+        ("  route=fwd1 (one launch, shipped geometry)", fwd("fwd1")),
+    ]
+    # every gemm_fwd1_kernel geometry kept for measurement ("s": B
+    # loaded strided instead of through the transposing LDS image)
+    rows += [("  route=fwd1 tile %s" % v, fwd("fwd1", v))
+             for v in sorted(k for k in ops.GEMM_FWD1_VARIANTS if k)]
+    # both routes at the other sliced shapes of the one-launch tests
+    for m, n, k in ((128, 128, 256), (33, 40, 1024), (7, 4, 260),
+                    (65, 17, 300), (24, 40, 2560)):
+        a2 = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
+        w2 = torch.randn(k, n, device=dev, dtype=torch.bfloat16)
+        b2 = torch.randn(n, device=dev, dtype=torch.bfloat16)
+        for route in ("stripes", "fwd1"):
+            rows.append(("  [%dx%d]@[%dx%d] route=%s" % (m, k, k, n, route),
+                         fwd(route, None, a2, w2, b2)))
+    nstep = 1   # rows above the first one are alternatives, not step parts
+    step_rows = [
         ("fwd2 gemm+bias [100x100]@[100x10]",
          lambda: ops.gemm_bias_act(h, sm_w, sm_b)),
         ("softmax_xent fused fwd+bwd [100,10]",
@@ -79,10 +101,11 @@ def main():
          lambda: gb2.fill_(0.0)),
     ]
     total = 0.0
-    for name, fn in rows:
+    for i, (name, fn) in enumerate(rows + step_rows):
         us = t_us(fn)
         print("%-52s %8.2f us" % (name, us))
-        if not name.startswith(("torch", "null")):
+        if not name.startswith(("torch", "null")) and \
+                (i < nstep or i >= len(rows)):
             total += us
     print("%-52s %8.2f us" % ("SUM (step estimate)", total))
 
