@@ -21,7 +21,8 @@ shard_bag_offsets, bag_coefficients; and the worker-side coalescing of a row
 request (TF's unique / unsorted_segment_sum): coalesce_ids, segment_sum_rows;
 and the key index of hashed embedding tables (TF's MutableHashTable):
 HashIndex, hash_find, hash_find_or_insert, hash_rebuild, hash_gather,
-hash_init_rows, hash_init_new_rows.
+hash_init_rows, hash_init_new_rows, and eviction from it: hash_touch (use
+stamps), hash_compact (keep the flagged rows, dense again), hash_remove.
 """
 
 import collections
@@ -730,9 +731,9 @@ def hash_home(keys, slots):
 class HashIndex(object):
     """Key index of a hashed table with ``capacity`` rows on ``device``.
 
-    row_keys int64 [capacity] (HASH_EMPTY behind ``size``), size and dropped
-    int64 [1] on the device (reading them is the caller's sync), and on a
-    GPU the slot arrays slot_keys / slot_rows int64 [hash_slots(capacity)].
+    row_keys int64 [capacity] (HASH_EMPTY behind ``size``), size, dropped and
+    evicted (rows removed by ``hash_compact``) int64 [1] on the device
+    (reading them is the caller's sync), and on a GPU the slot arrays slot_keys / slot_rows int64 [hash_slots(capacity)].
     On the CPU the reference keeps a dict instead of slot arrays."""
 
     def __init__(self, capacity, device="cpu"):
@@ -745,6 +746,7 @@ class HashIndex(object):
                                    dtype=torch.int64, device=self.device)
         self.size = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.dropped = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.evicted = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._alloc_slots()
 
     def _alloc_slots(self):
@@ -787,6 +789,7 @@ class HashIndex(object):
         self.row_keys[:n] = keys.to(self.device)
         self.size.fill_(n)
         self.dropped.zero_()
+        self.evicted.zero_()
         hash_rebuild(self)
 
 
@@ -860,6 +863,111 @@ def hash_rebuild(index):
         return
     n = int(index.size)
     index._map = {k: r for r, k in enumerate(index.row_keys[:n].tolist())}
+
+
+# Eviction. The GPU index has no deletion (a key sits before the first empty
+# slot of its probe sequence), so keys leave by COMPACTION: the caller says
+# which rows stay, the survivors are made dense again in every tensor that
+# is indexed by row, and the key -> row mapping is rebuilt.
+
+@torch.no_grad()
+def hash_touch(rows, last_used, step):
+    """Use stamps: last_used[rows[i]] = step for every position with
+    0 <= rows[i] < capacity; last_used int64 [capacity] on the rows' device.
+    GPU: one lane per position, plain stores, nothing read back."""
+    if rows.dim() != 1 or rows.dtype != torch.int64:
+        raise ValueError("hash_touch: rows must be int64 [n]")
+    if last_used.dim() != 1 or last_used.dtype != torch.int64 or \
+            last_used.device != rows.device or not last_used.is_contiguous():
+        raise ValueError("hash_touch: last_used must be a contiguous int64 "
+                         "[capacity] on the rows' device")
+    if rows.is_cuda:
+        _ext().hash_touch(rows.contiguous(), last_used, int(step))
+        return
+    ok = (rows >= 0) & (rows < last_used.numel())
+    last_used[rows[ok]] = int(step)
+
+
+def _hash_compact_check(index, keep, tables, last_used):
+    cap, dev = index.capacity, index.row_keys.device
+    if keep.dtype != torch.bool or tuple(keep.shape) != (cap,) or \
+            keep.device != dev:
+        raise ValueError("hash_compact: keep must be bool [capacity] = [%d] "
+                         "on %s, got %s %s on %s"
+                         % (cap, dev, keep.dtype, tuple(keep.shape),
+                            keep.device))
+    tables = list(tables)
+    if len(tables) > 4:
+        raise ValueError("hash_compact: at most 4 row tensors")
+    for t in tables:
+        if t.dim() != 2 or t.shape[0] != cap or t.device != dev or \
+                t.dtype not in (torch.float32, torch.bfloat16) or \
+                t.shape[1] != tables[0].shape[1] or not t.is_contiguous():
+            raise ValueError("hash_compact: every row tensor must be a "
+                             "contiguous fp32 or bf16 [capacity, D] = [%d, "
+                             "D] on %s, got %s %s on %s"
+                             % (cap, dev, t.dtype, tuple(t.shape), t.device))
+    if last_used is not None and (
+            last_used.dtype != torch.int64 or last_used.device != dev or
+            tuple(last_used.shape) != (cap,) or
+            not last_used.is_contiguous()):
+        raise ValueError("hash_compact: last_used must be a contiguous int64 "
+                         "[capacity] on the index's device")
+    return tables
+
+
+@torch.no_grad()
+def hash_compact(index, keep, tables, last_used=None):
+    """Keep the rows r < size with keep[r] and evict the others, in place:
+    afterwards the K survivors own rows 0 .. K-1 of ``index.row_keys``, of
+    every tensor of ``tables`` (at most four fp32 or bf16 [capacity, D]: a
+    table's master, shadow and optimizer state) and of ``last_used`` (int64
+    [capacity], optional). keep is bool [capacity] on the index's device;
+    what it says at and beyond size is ignored. Returns nothing, reads
+    nothing back.
+
+    Hole filling, not a stable shift: the evicted rows below K (ascending)
+    receive the kept rows at or above K (ascending), pair by pair, so a
+    survivor below K keeps its row, at most min(evicted, survivors) rows
+    move and no second copy of a tensor is needed. Then row_keys[K:size] =
+    HASH_EMPTY, size = K, ``index.evicted`` grows by size - K and the
+    key -> row mapping is rebuilt. Rows >= K of the row tensors are not
+    written: they keep stale data until ``hash_init_new_rows`` hands them
+    out again. The GPU (csrc/hash.hip) equals this reference integer for
+    integer and bit for bit."""
+    tables = _hash_compact_check(index, keep, tables, last_used)
+    if index.device.type != "cpu":
+        _ext().hash_compact(
+            index.slot_keys, index.slot_rows, index.row_keys, index.size,
+            index.evicted, keep.contiguous(), tables,
+            last_used if last_used is not None
+            else torch.empty(0, dtype=torch.int64, device=keep.device))
+        return
+    size = min(max(int(index.size), 0), index.capacity)
+    kept = keep[:size]
+    K = int(kept.sum())
+    r = torch.arange(size)
+    holes = r[:K][~kept[:K]]
+    movers = r[K:][kept[K:]]
+    for t in [index.row_keys] + tables + \
+            ([last_used] if last_used is not None else []):
+        t[holes] = t[movers]
+    index.row_keys[K:size] = HASH_EMPTY
+    index.size.fill_(K)
+    index.evicted += size - K
+    hash_rebuild(index)
+
+
+@torch.no_grad()
+def hash_remove(index, keys, tables, last_used=None):
+    """Remove ``keys`` from the index: ``hash_compact`` with keep = every
+    row but the ones ``hash_find`` returns for the keys. Absent keys,
+    duplicates and HASH_EMPTY are ignored. No host sync."""
+    rows = hash_find(index, keys)
+    cap = index.capacity
+    keep = torch.ones(cap + 1, dtype=torch.bool, device=rows.device)
+    keep[torch.where(rows < 0, torch.full_like(rows, cap), rows)] = False
+    hash_compact(index, keep[:cap], tables, last_used)
 
 
 def _rows_or_zero(table, rows):

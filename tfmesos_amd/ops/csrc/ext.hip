@@ -97,6 +97,13 @@ void launch_hash_gather(const long*, const long*, const long*, const bf16_t*,
 void launch_hash_init_rows(const long*, const long*, const bool*, float*,
                            bf16_t*, float*, float*, long, long, int, long,
                            long, long, float, hipStream_t);
+void launch_hash_touch(const long*, long*, long, long, long, hipStream_t);
+void launch_hash_compact_flags(const bool*, const long*, int*, long*, long,
+                               hipStream_t);
+void launch_hash_compact_move(const int*, const long*, const long*, long*,
+                              long*, void* const*, const int*, const int*,
+                              int, long*, long*, long*, long*, long,
+                              hipStream_t);
 void launch_relu_bwd(const bf16_t*, const bf16_t*, bf16_t*, long,
                      hipStream_t);
 void launch_add_n(const bf16_t* const*, int, bf16_t*, long, hipStream_t);
@@ -1410,6 +1417,90 @@ void hash_init_new_rows(torch::Tensor keys, torch::Tensor rows,
                         cur_stream());
 }
 
+// last_used[rows[i]] = step for every rows[i] in [0, capacity).
+void hash_touch(torch::Tensor rows, torch::Tensor last_used, long step) {
+  const long n = hash_keys(rows);
+  TORCH_CHECK(hash_i64(last_used) && last_used.device() == rows.device(),
+              "hash_touch: last_used must be contiguous i64 [capacity] on "
+              "the rows' GPU");
+  if (n == 0 || last_used.numel() == 0) return;
+  launch_hash_touch(rows.data_ptr<long>(), last_used.data_ptr<long>(), n,
+                    last_used.numel(), step, cur_stream());
+}
+
+// Compaction by hole filling (hash.hip): the rows of [0, size) with keep set
+// become rows [0, K) in every tensor of tables, in row_keys and in last_used
+// (numel 0: none); then the slot arrays are rebuilt. The scan of the flags
+// and the slot clear are plumbing; no host sync.
+void hash_compact(torch::Tensor slot_keys, torch::Tensor slot_rows,
+                  torch::Tensor row_keys, torch::Tensor size,
+                  torch::Tensor evicted, torch::Tensor keep,
+                  std::vector<torch::Tensor> tables,
+                  torch::Tensor last_used) {
+  const long H = hash_slots(slot_keys, slot_rows);
+  hash_counters(row_keys, size, H);
+  const long capacity = row_keys.numel();
+  const auto dev = row_keys.device();
+  TORCH_CHECK(hash_i64(evicted) && evicted.numel() == 1 &&
+              evicted.device() == dev && size.device() == dev &&
+              slot_keys.device() == dev && slot_rows.device() == dev,
+              "hash_compact: evicted must be i64 [1] on the index's GPU");
+  TORCH_CHECK(keep.is_cuda() && keep.device() == dev &&
+              keep.scalar_type() == torch::kBool && keep.dim() == 1 &&
+              keep.is_contiguous() && keep.numel() == capacity,
+              "hash_compact: keep must be contiguous bool [capacity] = [",
+              capacity, "] on the index's GPU");
+  TORCH_CHECK(tables.size() <= 4, "hash_compact: at most 4 row tensors");
+  void* bases[4] = {nullptr, nullptr, nullptr, nullptr};
+  int row_bytes[4] = {0, 0, 0, 0}, elem_bytes[4] = {0, 0, 0, 0};
+  int count = 0;
+  for (const auto& t : tables) {
+    const bool f32 = t.scalar_type() == torch::kFloat32;
+    TORCH_CHECK(t.is_cuda() && t.device() == dev && t.dim() == 2 &&
+                t.is_contiguous() && t.size(0) == capacity &&
+                (f32 || t.scalar_type() == torch::kBFloat16),
+                "hash_compact: every row tensor must be contiguous fp32 or "
+                "bf16 [capacity, D] on the index's GPU");
+    TORCH_CHECK(t.size(1) == tables[0].size(1),
+                "hash_compact: the row tensors must share one width D");
+    const long bytes = t.size(1) * (f32 ? 4 : 2);
+    TORCH_CHECK(bytes <= (long)INT_MAX, "hash_compact: D too large");
+    if (bytes == 0) continue;
+    bases[count] = t.data_ptr();
+    row_bytes[count] = (int)bytes;
+    elem_bytes[count] = f32 ? 4 : 2;
+    ++count;
+  }
+  long* stamps = nullptr;
+  if (last_used.numel() != 0) {
+    TORCH_CHECK(hash_i64(last_used) && last_used.device() == dev &&
+                last_used.numel() == capacity,
+                "hash_compact: last_used must be contiguous i64 [capacity] "
+                "on the index's GPU");
+    stamps = last_used.data_ptr<long>();
+  }
+  auto opt = row_keys.options();
+  auto flags = torch::empty({capacity}, opt.dtype(torch::kInt32));
+  auto old_size = torch::empty({1}, opt);
+  auto plan = torch::empty({2, capacity}, opt);   // [0] holes, [1] movers
+  launch_hash_compact_flags(keep.data_ptr<bool>(), size.data_ptr<long>(),
+                            flags.data_ptr<int>(), old_size.data_ptr<long>(),
+                            capacity, cur_stream());
+  auto incl = torch::cumsum(flags, 0, torch::kInt64);
+  long* pp = plan.data_ptr<long>();
+  launch_hash_compact_move(flags.data_ptr<int>(), incl.data_ptr<long>(),
+                           old_size.data_ptr<long>(), pp, pp + capacity,
+                           bases, row_bytes, elem_bytes, count,
+                           row_keys.data_ptr<long>(), stamps,
+                           size.data_ptr<long>(), evicted.data_ptr<long>(),
+                           capacity, cur_stream());
+  slot_keys.fill_((int64_t)LONG_MIN);
+  slot_rows.fill_(-1);
+  launch_hash_rebuild(row_keys.data_ptr<long>(), size.data_ptr<long>(),
+                      slot_keys.data_ptr<long>(), slot_rows.data_ptr<long>(),
+                      H, capacity, cur_stream());
+}
+
 torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor act) {
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16 &&
               dy.is_contiguous() && act.is_contiguous() &&
@@ -2223,6 +2314,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("master"), py::arg("shadow"), py::arg("states"),
         py::arg("seed"), py::arg("key_mul"), py::arg("key_add"),
         py::arg("scale"));
+  m.def("hash_touch", &hash_touch, "last_used[rows] = step",
+        py::arg("rows"), py::arg("last_used"), py::arg("step"));
+  m.def("hash_compact", &hash_compact,
+        "keep the flagged rows, dense again, in every row tensor; rebuild",
+        py::arg("slot_keys"), py::arg("slot_rows"), py::arg("row_keys"),
+        py::arg("size"), py::arg("evicted"), py::arg("keep"),
+        py::arg("tables"), py::arg("last_used"));
   m.def("relu_bwd", &relu_bwd);
   m.def("colsum", &colsum, py::arg("x"), py::arg("out"));
 }

@@ -56,6 +56,37 @@
 // 256-column tile) writes master, shadow and zeroed state rows for the
 // positions with is_new set. Every bound is checked; grids are sized
 // from n.
+//
+// Eviction. The slot array has no deletion, so keys leave by COMPACTION:
+// the caller says which rows stay (keep bool [capacity], read below size
+// only), the surviving rows are made dense again and the slot array is
+// rebuilt from row_keys. hash_touch keeps the use stamps a policy builds
+// keep from: last_used[rows[i]] = step, one lane per position, plain stores
+// (duplicates store the same value).
+//
+// compact(keep, row tensors, last_used) — hole filling. With K kept rows
+// below size, the evicted rows below K (holes, ascending) receive the kept
+// rows at or above K (movers, ascending), pair by pair: sources and
+// destinations are disjoint, so the move runs in place with no second copy
+// of a table, and it moves min(evicted, survivors) rows at the most. Four
+// kernels and one scan, nothing read back, no kernel reads what another
+// lane of the same kernel writes:
+//   1. flags: flag[r] = r < size and keep[r]; lane 0 saves size.
+//   *  incl = the inclusive scan of the flags (torch.cumsum, plumbing);
+//      K = incl[capacity - 1].
+//   2. plan: an evicted row r < K is hole number r - incl[r]; a kept row
+//      r >= K is mover number incl[r] - 1 - incl[K - 1].
+//   3. move: one wave per (hole, mover) pair copies the row in EVERY row
+//      tensor (master, shadow, state: raw bytes, 16 per lane when the row
+//      size and the base allow, else one element per lane), and lane 0 the
+//      row's key and stamp. The number of pairs is known on the device
+//      only: a grid of fixed size (at most 2048 blocks of 4 waves) strides
+//      over the pairs.
+//   4. finalize: row_keys[K:size] = EMPTY; size = K, evicted += size - K,
+//      from the size kernel 1 saved.
+//   Then the slot arrays are cleared and rebuild_kernel inserts
+//   row_keys[0:K]. Rows >= K of the row tensors keep stale data; the init
+//   kernel overwrites a row when it is handed out again.
 #include "common.h"
 
 #include <climits>
@@ -286,11 +317,168 @@ __global__ __launch_bounds__(WAVES * WAVE) void init_rows_kernel(
   if (s2) st_tile<float, VEC>(s2 + row * D, c0, lane, D, zero);
 }
 
+// Use stamps: last_used[rows[i]] = step. Duplicates store the same value.
+__global__ __launch_bounds__(BLOCK) void touch_kernel(
+    const long* __restrict__ rows, long* __restrict__ last_used, long n,
+    long capacity, long step) {
+  const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const long r = rows[i];
+  if (r >= 0 && r < capacity) last_used[r] = step;
+}
+
+// compact 1: flags[r] = row r is live and kept; lane 0 saves the size the
+// later kernels work from (no lane of this kernel reads old_size).
+__global__ __launch_bounds__(BLOCK) void keep_flag_kernel(
+    const bool* __restrict__ keep, const long* __restrict__ size,
+    int* __restrict__ flags, long* __restrict__ old_size, long capacity) {
+  const long r = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (r >= capacity) return;
+  long sz = size[0];
+  sz = sz < 0 ? 0 : (sz > capacity ? capacity : sz);
+  flags[r] = r < sz && keep[r];
+  if (r == 0) old_size[0] = sz;
+}
+
+// compact 2: holes (evicted rows below K) and movers (kept rows at or above
+// K), each written at its rank. incl is the inclusive scan of flags, K =
+// incl[capacity - 1]; both lists have K - incl[K - 1] entries.
+__global__ __launch_bounds__(BLOCK) void plan_kernel(
+    const int* __restrict__ flags, const long* __restrict__ incl,
+    const long* __restrict__ old_size, long* __restrict__ holes,
+    long* __restrict__ movers, long capacity) {
+  const long r = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (r >= capacity || r >= old_size[0]) return;
+  const long K = incl[capacity - 1];
+  if (r < K) {
+    if (!flags[r]) holes[r - incl[r]] = r;    // evicted rows in [0, r] - 1
+  } else if (flags[r]) {
+    const long below = K > 0 ? incl[K - 1] : 0;
+    movers[incl[r] - 1 - below] = r;          // kept rows in [K, r] - 1
+  }
+}
+
+// The row tensors that travel with a row: base, bytes per row, and the
+// access width (16, or the element size when D or the base rule 16 out).
+struct CompactTabs {
+  char* base[4];
+  int row_bytes[4];
+  int width[4];
+  int count;
+};
+
+template <typename U>
+DEVINL void copy_row(const char* __restrict__ src, char* __restrict__ dst,
+                     int row_bytes, int lane) {
+  for (int c = lane * (int)sizeof(U); c < row_bytes; c += WAVE * (int)sizeof(U))
+    *(U*)(dst + c) = *(const U*)(src + c);
+}
+
+// compact 3: one wave per mover copies row movers[j] onto row holes[j] in
+// every tensor; sources (>= K) and destinations (< K) are disjoint. The
+// number of movers lives on the device, so a grid of fixed size strides
+// over them.
+__global__ __launch_bounds__(WAVES * WAVE) void move_kernel(
+    CompactTabs tabs, const long* __restrict__ incl,
+    const long* __restrict__ holes, const long* __restrict__ movers,
+    long* __restrict__ row_keys, long* __restrict__ last_used,
+    long capacity) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const long w0 = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  const long stride = (long)gridDim.x * WAVES;
+  const long K = incl[capacity - 1];
+  const long M = K > 0 && K <= capacity ? K - incl[K - 1] : 0;
+  for (long j = w0; j < M && j < capacity; j += stride) {   // wave-uniform
+    const long h = holes[j], m = movers[j];
+    if (h < 0 || h >= capacity || m < 0 || m >= capacity) continue;
+    if (lane == 0) {
+      row_keys[h] = row_keys[m];
+      if (last_used) last_used[h] = last_used[m];
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (t < tabs.count) {
+        const int rb = tabs.row_bytes[t];
+        const char* src = tabs.base[t] + m * rb;
+        char* dst = tabs.base[t] + h * rb;
+        if (tabs.width[t] == 16) copy_row<uint4>(src, dst, rb, lane);
+        else if (tabs.width[t] == 4) copy_row<unsigned>(src, dst, rb, lane);
+        else copy_row<unsigned short>(src, dst, rb, lane);
+      }
+    }
+  }
+}
+
+// compact 4: EMPTY behind the survivors, and the counters. No lane reads
+// size or evicted: the old size comes from kernel 1's copy.
+__global__ __launch_bounds__(BLOCK) void finalize_kernel(
+    const long* __restrict__ incl, const long* __restrict__ old_size,
+    long* __restrict__ row_keys, long* __restrict__ size,
+    long* __restrict__ evicted, long capacity) {
+  const long r = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (r >= capacity) return;
+  const long sz = old_size[0], K = incl[capacity - 1];
+  if (r >= K && r < sz) row_keys[r] = EMPTY;
+  if (r == 0) {
+    size[0] = K;
+    evicted[0] += sz - K;
+  }
+}
+
 inline dim3 lanes_grid(long n) {
   return dim3((unsigned)((n + BLOCK - 1) / BLOCK));
 }
 
 }  // namespace
+
+// rows [n], n > 0; last_used [capacity].
+void launch_hash_touch(const long* rows, long* last_used, long n,
+                       long capacity, long step, hipStream_t stream) {
+  hipLaunchKernelGGL(touch_kernel, lanes_grid(n), dim3(BLOCK), 0, stream, rows,
+                     last_used, n, capacity, step);
+}
+
+// Kernel 1 of a compaction. keep bool [capacity], flags int32 [capacity],
+// old_size int64 [1]; capacity > 0.
+void launch_hash_compact_flags(const bool* keep, const long* size, int* flags,
+                               long* old_size, long capacity,
+                               hipStream_t stream) {
+  hipLaunchKernelGGL(keep_flag_kernel, lanes_grid(capacity), dim3(BLOCK), 0,
+                     stream, keep, size, flags, old_size, capacity);
+}
+
+// Kernels 2 to 4. incl: int64 inclusive scan of flags; holes / movers int64
+// [capacity]; bases / row_bytes / elem_bytes describe count <= 4 row tensors
+// of capacity rows; last_used [capacity] or null.
+void launch_hash_compact_move(const int* flags, const long* incl,
+                              const long* old_size, long* holes, long* movers,
+                              void* const* bases, const int* row_bytes,
+                              const int* elem_bytes, int count,
+                              long* row_keys, long* last_used, long* size,
+                              long* evicted, long capacity,
+                              hipStream_t stream) {
+  hipLaunchKernelGGL(plan_kernel, lanes_grid(capacity), dim3(BLOCK), 0, stream,
+                     flags, incl, old_size, holes, movers, capacity);
+  CompactTabs tabs = {};
+  tabs.count = count;
+  for (int t = 0; t < count; ++t) {
+    tabs.base[t] = (char*)bases[t];
+    tabs.row_bytes[t] = row_bytes[t];
+    const bool wide = (row_bytes[t] % 16) == 0 &&
+                      ((uintptr_t)bases[t] % 16) == 0;
+    tabs.width[t] = wide ? 16 : elem_bytes[t];
+  }
+  // at most capacity / 2 movers; MOVE_BLOCKS blocks fill the device
+  constexpr long MOVE_BLOCKS = 2048;
+  long blocks = (capacity / 2 + WAVES) / WAVES;
+  if (blocks > MOVE_BLOCKS) blocks = MOVE_BLOCKS;
+  hipLaunchKernelGGL(move_kernel, dim3((unsigned)blocks), dim3(WAVES * WAVE),
+                     0, stream, tabs, incl, holes, movers, row_keys,
+                     last_used, capacity);
+  hipLaunchKernelGGL(finalize_kernel, lanes_grid(capacity), dim3(BLOCK), 0,
+                     stream, incl, old_size, row_keys, size, evicted,
+                     capacity);
+}
 
 // keys [n], n > 0 -> rows [n].
 void launch_hash_find(const long* keys, const long* slot_keys,

@@ -71,6 +71,9 @@ client and the wire format serve it as they serve an ``EmbeddingTable``; a
 new row's initial value is a pure function of (seed, key, column), so
 ``HashedEmbeddingTable.shard_of`` shards (homes ``[ranks]``, ``rows={name:
 ops.HASH_KEY_SPACE}``, strategy "mod") equal the unsharded table key for key.
+Keys leave again through ``remove`` / ``evict`` or the automatic idle policy
+(``evict_every=, max_idle=``): ``ops.hash_compact`` keeps the rows dense by
+moving the highest survivors into the holes, in every per-row tensor.
 """
 
 import threading
@@ -498,8 +501,26 @@ class HashedEmbeddingTable(object):
       read as zero rows.
     * A full table: a new key gets no row (its pushes are dropped, its
       pulls read zeros) and ``stats()["dropped"]`` counts it, once per
-      request that names it; ``reserve`` makes room. There is no eviction
-      and no automatic growth.
+      request that names it; ``reserve`` or eviction makes room. There is
+      no automatic growth.
+    * Eviction: ``remove(keys)`` takes keys out explicitly; with use
+      tracking (``track_use=True``, or ``max_idle`` / ``evict_every``
+      given) every row carries the ``step`` of the last request that named
+      its key and ``evict(max_idle=, target_size=)`` drops idle rows or the
+      least recently used ones. ``evict_every=E`` with ``max_idle=M`` (both
+      or neither, M >= 1) runs ``evict(max_idle=M)`` after every push that
+      leaves ``step % E == 0``, under the push's lock hold and without a
+      host sync. Rows stay dense in ``[0, size)``: the survivors of the
+      highest rows fill the holes (``ops.hash_compact``), so ROW NUMBERS
+      CHANGE at an eviction while a key's row content travels with it. An
+      evicted key that is named again is a first-seen key: initial row,
+      zero optimizer state. A stamp is the table's ``step`` at the request:
+      a push stamps the step it starts from, pulls do not advance it.
+      Serving row pulls (``insert_on_pull=False``) stay the read-only
+      one-launch ``ops.hash_gather`` and do NOT stamp, so a key that is only
+      ever served looks idle; every other request stamps the rows it names.
+      Without tracking nothing is allocated and no request launches
+      anything more than before.
     * Sharding: ``shard_of`` shards take keys in ``[0,
       ops.HASH_KEY_SPACE)`` = [0, 2**62) and the "mod" strategy only
       (``SparseWorkerClient(table_homes={name: [ranks]}, rows={name:
@@ -513,9 +534,21 @@ class HashedEmbeddingTable(object):
 
     def __init__(self, name, dim, capacity, device="cpu", lr=0.01, seed=0,
                  optimizer="sgd", insert_on_pull=True, key_mul=1, key_add=0,
+                 track_use=False, max_idle=None, evict_every=None,
                  **hparams):
         """key_mul / key_add (``shard_of`` sets them): local key k stands
-        for the global key k * key_mul + key_add in the initialiser."""
+        for the global key k * key_mul + key_add in the initialiser.
+        track_use / max_idle / evict_every: use stamps and the automatic
+        eviction policy (class docstring)."""
+        if (max_idle is None) != (evict_every is None):
+            raise ValueError("max_idle and evict_every go together, got "
+                             "max_idle=%r, evict_every=%r"
+                             % (max_idle, evict_every))
+        if max_idle is not None and (int(max_idle) < 1 or
+                                     int(evict_every) < 1):
+            raise ValueError("need max_idle >= 1 and evict_every >= 1, got "
+                             "max_idle=%r, evict_every=%r"
+                             % (max_idle, evict_every))
         if optimizer not in self._HPARAMS:
             raise ValueError("unknown sparse optimizer %r (have %s)"
                              % (optimizer, sorted(self._HPARAMS)))
@@ -541,6 +574,13 @@ class HashedEmbeddingTable(object):
             names = ("momentum_buf",)
         self._state_names = names
         self._alloc(self.index.capacity)
+        self.track_use = bool(track_use or max_idle is not None)
+        self.max_idle = None if max_idle is None else int(max_idle)
+        self.evict_every = None if evict_every is None else int(evict_every)
+        # the step of the last request that named row r's key
+        self.last_used = torch.zeros(
+            self.index.capacity, dtype=torch.int64,
+            device=self.device) if self.track_use else None
         self.lock = threading.Lock()
 
     @property
@@ -570,7 +610,10 @@ class HashedEmbeddingTable(object):
         which is what the row initialiser sees, so the shards hold, key
         for key, the rows of ``HashedEmbeddingTable(name, dim, ..., **kw)``.
         ``capacity`` is this shard's own. Global keys lie in
-        [0, ops.HASH_KEY_SPACE)."""
+        [0, ops.HASH_KEY_SPACE). ``track_use`` / ``max_idle`` /
+        ``evict_every`` pass through: every shard stamps and evicts by its
+        OWN ``step``, which moves in lockstep with the other shards' as
+        long as every push reaches every shard (the stock client's do)."""
         if not 1 <= num_shards <= 64 or not 0 <= shard < num_shards:
             raise ValueError("need 1 <= num_shards <= 64 and 0 <= shard < "
                              "num_shards, got shard %r of %r"
@@ -583,12 +626,75 @@ class HashedEmbeddingTable(object):
         ``insert`` absent keys get rows, initialised in the same breath."""
         keys = keys.to(self.device)
         if not insert:
-            return ops.hash_find(self.index, keys)
-        rows, is_new = ops.hash_find_or_insert(self.index, keys)
-        ops.hash_init_new_rows(keys, rows, is_new, self.master, self.shadow,
-                               list(self.state.values()), self.seed,
-                               self.key_mul, self.key_add)
+            rows = ops.hash_find(self.index, keys)
+        else:
+            rows, is_new = ops.hash_find_or_insert(self.index, keys)
+            ops.hash_init_new_rows(keys, rows, is_new, self.master,
+                                   self.shadow, list(self.state.values()),
+                                   self.seed, self.key_mul, self.key_add)
+        if self.track_use:      # new rows included: they are in ``rows``
+            ops.hash_touch(rows, self.last_used, self.step)
         return rows
+
+    def _row_tensors(self):
+        """Everything indexed by row besides row_keys and the stamps."""
+        return [self.master, self.shadow] + list(self.state.values())
+
+    def _auto_evict(self):
+        """The automatic policy, after a push's apply (lock held)."""
+        if self.evict_every and self.step % self.evict_every == 0:
+            self._evict(self.max_idle, None)
+
+    def _evict(self, max_idle, target_size):
+        """One compaction for both rules (lock held)."""
+        cap = self.index.capacity
+        lu = self.last_used
+        keep = torch.arange(cap, device=self.device) < self.index.size
+        if max_idle is not None:
+            keep &= lu >= self.step - int(max_idle)
+        if target_size is not None:
+            # stable ascending sort with every non-survivor in front: the
+            # survivors follow in (last_used, row) order and the last
+            # target_size entries are the ones to keep
+            first = torch.full_like(lu, ops.HASH_EMPTY)
+            order = torch.sort(torch.where(keep, lu, first), stable=True)[1]
+            newest = torch.zeros_like(keep)
+            newest[order[max(0, cap - int(target_size)):]] = True
+            keep &= newest
+        ops.hash_compact(self.index, keep, self._row_tensors(), lu)
+
+    def remove(self, keys):
+        """Take ``keys`` out of the table (absent keys, duplicates and
+        ``ops.HASH_EMPTY`` are ignored); works with or without use
+        tracking. The rows behind them are reused; no host sync."""
+        with self.lock:
+            ops.hash_remove(self.index, keys.to(self.device),
+                            self._row_tensors(), self.last_used)
+
+    def evict(self, max_idle=None, target_size=None):
+        """Evict by use stamp, in ONE compaction (``ops.hash_compact``):
+
+        * ``max_idle=M`` (>= 0): every row with ``step - last_used > M``
+          goes. No host sync.
+        * ``target_size=T`` (>= 0), applied to what the idle rule leaves: if
+          more than T rows survive, the ones with the smallest
+          ``(last_used, row)`` go until T remain — least recently used
+          first, the lower row first among equal stamps. It runs a stable
+          ``torch.sort`` over the stamps of all ``capacity`` rows; it too
+          works on device tensors only and does not sync.
+
+        Needs use tracking and at least one of the two (ValueError)."""
+        if not self.track_use:
+            raise ValueError("evict: table %r does not track use (build it "
+                             "with track_use=True)" % self.name)
+        if max_idle is None and target_size is None:
+            raise ValueError("evict: give max_idle and / or target_size")
+        if (max_idle is not None and max_idle < 0) or \
+                (target_size is not None and target_size < 0):
+            raise ValueError("evict: max_idle and target_size must be >= 0, "
+                             "got %r, %r" % (max_idle, target_size))
+        with self.lock:
+            self._evict(max_idle, target_size)
 
     def pull(self, ids):
         """bf16 rows for the keys ``ids``; zero rows for keys without one."""
@@ -607,6 +713,7 @@ class HashedEmbeddingTable(object):
         lr = self.lr if lr is None else lr
         with self.lock:
             self._push_fused(self._rows(ids, True), grads, lr)
+            self._auto_evict()
 
     def pull_pooled(self, ids, offsets, weights=None, combiner="sum",
                     out_dtype=None):
@@ -627,11 +734,20 @@ class HashedEmbeddingTable(object):
             self._push_fused(self._rows(ids, True), bag_grads, lr,
                              offsets=offsets, weights=weights,
                              combiner=combiner)
+            self._auto_evict()
 
     def stats(self):
-        """{"size", "dropped", "capacity"} — THE place that syncs: the two
-        counters live on the device and nothing else reads them."""
+        """{"size", "dropped", "capacity"}, and "evicted" (rows removed by
+        ``evict`` / ``remove`` so far) on a table that tracks use — THE
+        place that syncs: the counters live on the device and nothing else
+        reads them."""
         with self.lock:
+            if self.track_use:
+                size, dropped, evicted = torch.cat(
+                    [self.index.size, self.index.dropped,
+                     self.index.evicted]).tolist()
+                return {"size": size, "dropped": dropped,
+                        "capacity": self.index.capacity, "evicted": evicted}
             size, dropped = torch.cat(
                 [self.index.size, self.index.dropped]).tolist()
             return {"size": size, "dropped": dropped,
@@ -649,16 +765,23 @@ class HashedEmbeddingTable(object):
                                          self.index.capacity))
             if capacity == self.index.capacity:
                 return
+            old = self.index.capacity
             self.index.reserve(capacity)
             self._alloc(capacity, (self.master, self.shadow, self.state))
+            if self.track_use:
+                stamps = torch.zeros(capacity, dtype=torch.int64,
+                                     device=self.device)
+                stamps[:old] = self.last_used
+                self.last_used = stamps
 
     def state_dict(self):
         """keys = row_keys[:size], the first ``size`` rows of master and
         optimizer state, step and seed (CPU copies); row r belongs to
-        keys[r]."""
+        keys[r]. A table that tracks use adds "last_used", the first
+        ``size`` stamps."""
         with self.lock:
             n = int(self.index.size)
-            return {
+            sd = {
                 "optimizer": self.optimizer,
                 "keys": self.index.row_keys[:n].cpu().clone(),
                 "master": self.master[:n].cpu().clone(),
@@ -667,6 +790,9 @@ class HashedEmbeddingTable(object):
                 "step": self.step,
                 "seed": self.seed,
             }
+            if self.track_use:
+                sd["last_used"] = self.last_used[:n].cpu().clone()
+            return sd
 
     def load_state_dict(self, sd):
         """Load into this table (any capacity >= the checkpoint's size):
@@ -693,6 +819,11 @@ class HashedEmbeddingTable(object):
             self.shadow[:n].copy_(self.master[:n].to(torch.bfloat16))
             self.step = int(sd["step"])
             self.seed = int(sd["seed"])
+            if self.track_use:      # no stamps saved: all used "just now"
+                if "last_used" in sd:
+                    self.last_used[:n].copy_(sd["last_used"])
+                else:
+                    self.last_used[:n].fill_(self.step)
 
 
 def make_sparse_pair_groups(ps_ranks, worker_ranks):
