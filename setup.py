@@ -17,6 +17,7 @@ from torch.utils.cpp_extension import BuildExtension, CUDAExtension  # noqa: E40
 CSRC = os.path.join("tfmesos_amd", "ops", "csrc")
 sources = [
     os.path.join(CSRC, "ext.hip"),
+    os.path.join(CSRC, "ext_sparse.hip"),
     os.path.join(CSRC, "apply.hip"),
     os.path.join(CSRC, "gemm.hip"),
     os.path.join(CSRC, "conv.hip"),

@@ -146,6 +146,58 @@ def test_hot_id_scalar_path_fp32():
     run_case("adam", 7, torch.float32, 1500, 1300, 1, seed=3)
 
 
+def _view_at(t, off):
+    """A copy of t on the GPU that starts ``off`` elements into its
+    storage (off = 1: contiguous, but not 16-byte aligned)."""
+    flat = torch.empty(t.numel() + off, dtype=t.dtype, device=DEV)
+    v = flat[off:off + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and (v.data_ptr() % 16 == 0) == (off == 0)
+    return v
+
+
+@pytest.mark.parametrize("unaligned", ["table", "grads"])
+def test_unaligned_views(unaligned):
+    """D % 4 == 0 but a base that is not 16-byte aligned: master, both Adam
+    moments and the shadow as views one element into their storage (fp32
+    grads aligned), or only the grads view misaligned. The launcher's
+    alignment rule sends both to the scalar path; what is asserted here is
+    the result, against the CPU reference as in run_case (which path ran
+    is not visible from Python)."""
+    Vs, D, opt = 64, 8, "adam"
+    gen = torch.Generator().manual_seed(11)
+    p_ref = torch.rand(Vs, D, generator=gen)
+    st_ref = [torch.rand(Vs, D, generator=gen) * 0.5 for _ in range(2)]
+    sh_ref = torch.full((Vs, D), SENTINEL, dtype=torch.bfloat16)
+    toff, goff = (1, 0) if unaligned == "table" else (0, 1)
+    p = _view_at(p_ref, toff)
+    st = [_view_at(s, toff) for s in st_ref]
+    sh = _view_at(sh_ref, toff)
+    touched = torch.zeros(Vs, dtype=torch.bool)
+    for k in (1, 2):
+        ids = mixed_ids(gen, 300)       # its invalid ids are invalid here too
+        g = dyadic(gen, ids.numel(), D)
+        gscale = 0.5 if k % 2 else 1.0
+        step(opt, p_ref, ids, g, st_ref, k, sh_ref, gscale)
+        before = [p.clone(), sh.clone()] + [s.clone() for s in st]
+        step(opt, p, ids.to(DEV), _view_at(g, goff), st, k, sh, gscale)
+        now = torch.zeros(Vs, dtype=torch.bool)
+        now[ids[(ids >= 0) & (ids < Vs)]] = True
+        touched |= now
+        print("unaligned %s step %d: max |master err| %.3g"
+              % (unaligned, k, (p.cpu() - p_ref).abs().max().item()))
+        assert torch.allclose(p.cpu(), p_ref, atol=1e-5)
+        for s, s_ref in zip(st, st_ref):
+            assert torch.allclose(s.cpu(), s_ref, atol=1e-5)
+        idle = (~now).to(DEV)
+        for t, t0 in zip([p, sh] + st, before):
+            assert torch.equal(t[idle], t0[idle])
+        tt = touched.to(DEV)
+        assert torch.equal(sh[tt], p[tt].to(torch.bfloat16))
+        assert (sh[~tt].float() == SENTINEL).all()
+    assert not touched[60:].any() and touched[:60].any()
+
+
 def test_bit_reproducible():
     gen = torch.Generator().manual_seed(9)
     D = 200

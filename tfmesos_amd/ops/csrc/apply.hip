@@ -8,6 +8,7 @@
 // refresh the bf16 broadcast shadow in the same pass — one HBM round trip,
 // float4-vectorized, grid sized to fill 256 CUs when the buffer is large.
 #include "common.h"
+#include "apply.h"
 
 namespace {
 

@@ -16,6 +16,7 @@
 //        fused) -> finalize (dgamma/dbeta + normalized sums) -> apply
 //        (dx in one pass)
 #include "common.h"
+#include "bn.h"
 
 namespace {
 

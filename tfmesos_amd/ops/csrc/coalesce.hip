@@ -30,12 +30,11 @@
 //   * hot ids: a run longer than CHUNK positions is cut into CHUNK-position
 //     pieces relative to the run start; the piece starting at sorted
 //     position p is summed by the wave of p's aligned 256-position window
-//     into fp32 scratch slot start/256 + piece (sparse_apply.hip's slot
-//     scheme: runs are disjoint and longer than 2 * 256, so slots never
-//     collide and n/256 + 1 slots suffice); the owning wave then adds the
-//     partials. A window holds at most one piece head per run; its wave
-//     finds the runs that overlap it by a binary search of seg and tests
-//     64 runs at a time, one per lane.
+//     (SLOT_DIV is also the width of pass 1's windows) into fp32 scratch
+//     slot start/256 + piece (the slot scheme of run_sum.h); the owning
+//     wave then adds the partials. A window holds at most one piece head
+//     per run; its wave finds the runs that overlap it by a binary search
+//     of seg and tests 64 runs at a time, one per lane.
 //   * SUMMATION ORDER. A run of at most CHUNK positions: fp32, starting
 //     from 0, one row after the other in run order (= request order inside
 //     an id: the sort is stable). A longer run: every piece that way, then
@@ -45,14 +44,12 @@
 //     clamped to [0, n]. The grids are sized from num, n and D.
 #include "common.h"
 
-#include "tile.h"
+#include "coalesce.h"
+#include "run_sum.h"
 
 namespace {
 
 constexpr int WAVES = 4;       // waves per block
-constexpr int CHUNK = 512;     // positions one wave sums
-constexpr int SLOT_DIV = 256;  // scratch slot of a long run = start/256 + k
-                               // (and the width of pass 1's windows)
 
 DEVINL bool is_head(const long* __restrict__ sorted, long j, long n) {
   return j < n && (j == 0 || sorted[j - 1] != sorted[j]);
@@ -101,20 +98,6 @@ __global__ __launch_bounds__(WAVES * WAVE) void coalesce_scatter_kernel(
   }
   const long p = perm[j];
   if (p >= 0 && p < n) inverse[p] = rank;
-}
-
-DEVINL long clamp_pos(long p, long n) { return p < 0 ? 0 : (p > n ? n : p); }
-
-// The row's tile, or zeros for the row -1 (r is wave-uniform).
-template <typename T, int VEC>
-DEVINL void ld_row(const T* __restrict__ rows, long r, int c0, int lane,
-                   int D, float (&v)[ACC]) {
-  if (r >= 0) {
-    ld_tile<T, VEC>(rows + r * D, c0, lane, D, v);
-  } else {
-#pragma unroll
-    for (int e = 0; e < ACC; ++e) v[e] = 0.f;
-  }
 }
 
 // acc += rows[perm[j]] for j in [pos, pos + cnt), in that order. All 64
@@ -240,13 +223,10 @@ void segment_typed(const T* rows, const long* perm, const long* seg,
                    hipStream_t stream) {
   const int tiles = (D + TILE - 1) / TILE;
   const dim3 block(WAVES * WAVE);
-  const long slots = n > CHUNK ? n / SLOT_DIV + 1 : 0;
+  const long slots = run_scratch_rows(n);
   const dim3 grid1((unsigned)((slots * tiles + WAVES - 1) / WAVES));
   const dim3 grid2((unsigned)((num * tiles + WAVES - 1) / WAVES));
-  // vector path needs 16-byte aligned rows: D % 4 == 0 and aligned bases
-  const uintptr_t bases = (uintptr_t)rows | (uintptr_t)out |
-                          (uintptr_t)scratch;
-  if ((D % 4) == 0 && (bases % 16) == 0) {
+  if (tile_vec4(D, rows, out, scratch)) {
     if (slots > 0)
       hipLaunchKernelGGL((segment_partial_kernel<T, 4>), grid1, block, 0,
                          stream, rows, perm, seg, scratch, n, num, slots, D,
@@ -290,14 +270,9 @@ void launch_coalesce_scatter(const long* sorted, const long* perm,
                      W);
 }
 
-// fp32 scratch rows segment_sum_rows needs for n positions.
-long segment_scratch_rows(long n) {
-  return n > CHUNK ? n / SLOT_DIV + 1 : 0;
-}
-
 // rows [n,D] fp32 or bf16, perm [n], seg [>= num+1] -> out [num,D] fp32 or
-// bf16. scratch: fp32 [segment_scratch_rows(n), D] (may be null when 0
-// rows). n, num, D > 0.
+// bf16. scratch: fp32 [run_scratch_rows(n), D] (may be null when 0 rows).
+// n, num, D > 0.
 void launch_segment_sum_rows(const void* rows, bool r_bf16, const long* perm,
                              const long* seg, float* scratch, void* out,
                              bool o_bf16, long n, long num, int D,

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv.h"
 
 namespace {
 

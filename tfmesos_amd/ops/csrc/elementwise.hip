@@ -1,6 +1,7 @@
 // Elementwise / reduction helpers for the explicit backward path:
 // relu_bwd (dx = dy * (act>0)) and colsum (bias gradients).
 #include "common.h"
+#include "elementwise.h"
 
 namespace {
 

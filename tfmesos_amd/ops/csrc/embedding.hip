@@ -6,6 +6,7 @@
 // row; gather streams rows out (bf16 or fp32 table), scatter-add
 // accumulates fp32 gradients with atomics (duplicate ids correct).
 #include "common.h"
+#include "embedding.h"
 
 namespace {
 

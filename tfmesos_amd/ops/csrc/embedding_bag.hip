@@ -17,6 +17,7 @@
 //   * a single very long bag stays with one wave per tile (no chunk rule
 //     on the forward side).
 #include "common.h"
+#include "embedding_bag.h"
 
 #include "bag.h"
 #include "tile.h"
@@ -91,9 +92,7 @@ void launch_typed(const T* table, const long* ids, const long* offsets,
   const long waves = B * tiles;
   const dim3 block(WAVES * WAVE);
   const dim3 grid((unsigned)((waves + WAVES - 1) / WAVES));
-  // vector path needs 16-byte aligned rows: D % 4 == 0 and aligned bases
-  const uintptr_t bases = (uintptr_t)table | (uintptr_t)out;
-  if ((D % 4) == 0 && (bases % 16) == 0)
+  if (tile_vec4(D, table, out))
     hipLaunchKernelGGL((embedding_bag_kernel<T, O, 4>), grid, block, 0,
                        stream, table, ids, offsets, weights, out, B, n, D, V,
                        tiles, (int)mean);

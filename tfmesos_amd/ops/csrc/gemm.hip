@@ -34,6 +34,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "gemm.h"
 #include "mlp_head.h"
 
 namespace {

@@ -88,6 +88,7 @@
 //   row_keys[0:K]. Rows >= K of the row tensors keep stale data; the init
 //   kernel overwrites a row when it is handed out again.
 #include "common.h"
+#include "hash.h"
 
 #include <climits>
 
@@ -547,9 +548,7 @@ void launch_hash_init_rows(const long* keys, const long* rows,
                            hipStream_t stream) {
   const int tiles = (D + TILE - 1) / TILE;
   const dim3 grid((unsigned)((n * tiles + WAVES - 1) / WAVES));
-  const uintptr_t bases = (uintptr_t)master | (uintptr_t)shadow |
-                          (uintptr_t)s1 | (uintptr_t)s2;
-  if ((D % 4) == 0 && (bases % 16) == 0)
+  if (tile_vec4(D, master, shadow, s1, s2))
     hipLaunchKernelGGL(init_rows_kernel<4>, grid, dim3(WAVES * WAVE), 0,
                        stream, keys, rows, is_new, master, shadow, s1, s2, n,
                        V, D, tiles, seed, key_mul, key_add, scale);

@@ -26,9 +26,9 @@
 //   Fixed slots, no atomics => two runs give identical bits. Grids are
 //   sized from n; nothing is read back.
 //
-// Row permute + cast: out[j] = cast(rows[perm[j]]), one wave per row,
-// f32x4 / bf16x4 when D % 4 == 0 and the bases are 16-byte aligned,
-// scalar otherwise (the split of embedding_bag.hip).
+// Row permute + cast: out[j] = cast(rows[perm[j]]), one wave per row, in
+// 256-column tiles (tile.h): f32x4 / bf16x4 when D % 4 == 0 and the bases
+// are 16-byte aligned, scalar otherwise.
 //
 // Per-shard CSR: the partition is stable, so perm is increasing inside a
 // shard and every bag stays contiguous there:
@@ -40,6 +40,8 @@
 #include "common.h"
 
 #include "bag.h"
+#include "partition.h"
+#include "run_sum.h"
 
 namespace {
 
@@ -133,48 +135,14 @@ __global__ __launch_bounds__(WAVES * WAVE) void permute_rows_kernel(
   const int lane = threadIdx.x & (WAVE - 1);
   const long j = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
   if (j >= n_out) return;   // wave-uniform
-  const long src = perm[j];
-  const bool ok = src >= 0 && src < n_rows;   // else a zero row
-  const T* __restrict__ in = rows + (ok ? src : 0) * D;
-  O* __restrict__ dst = out + j * D;
-  for (int c = lane * VEC; c < D; c += WAVE * VEC) {
-    float v[VEC];
-    if constexpr (VEC == 4) {
-      if constexpr (sizeof(T) == 2) {
-        const bf16x4 t = *(const bf16x4*)(const __bf16*)(in + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (float)t[e];
-      } else {
-        const f32x4 t = *(const f32x4*)(in + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = t[e];
-      }
-    } else {
-      if constexpr (sizeof(T) == 2) v[0] = bf2f(*(const bf16_t*)(in + c));
-      else v[0] = *(const float*)(in + c);
-    }
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) v[e] = ok ? v[e] : 0.f;
-    if constexpr (VEC == 4) {
-      if constexpr (sizeof(O) == 2) {
-        bf16x4 t;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) t[e] = (__bf16)v[e];
-        *(bf16x4*)(__bf16*)(dst + c) = t;
-      } else {
-        f32x4 t;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) t[e] = v[e];
-        *(f32x4*)(dst + c) = t;
-      }
-    } else {
-      if constexpr (sizeof(O) == 2) *(bf16_t*)(dst + c) = f2bf(v[0]);
-      else *(float*)(dst + c) = v[0];
-    }
+  long src = perm[j];
+  if (src >= n_rows) src = -1;   // outside [0, n_rows): a zero row
+  for (int c0 = 0; c0 < D; c0 += TILE) {
+    float v[ACC];
+    ld_row<T, VEC>(rows, src, c0, lane, D, v);
+    st_tile<O, VEC>(out + j * D, c0, lane, D, v);
   }
 }
-
-DEVINL long clamp_pos(long p, long n) { return p < 0 ? 0 : (p > n ? n : p); }
 
 // out[s * (B+1) + b], b in [0, B]: one thread per element.
 __global__ __launch_bounds__(WAVES * WAVE) void shard_bag_offsets_kernel(
@@ -216,9 +184,7 @@ void permute_typed(const T* rows, const long* perm, O* out, long n_out,
                    long n_rows, int D, hipStream_t stream) {
   const dim3 block(WAVES * WAVE);
   const dim3 grid((unsigned)((n_out + WAVES - 1) / WAVES));
-  // vector path needs 16-byte aligned rows: D % 4 == 0 and aligned bases
-  const uintptr_t bases = (uintptr_t)rows | (uintptr_t)out;
-  if ((D % 4) == 0 && (bases % 16) == 0)
+  if (tile_vec4(D, rows, out))
     hipLaunchKernelGGL((permute_rows_kernel<T, O, 4>), grid, block, 0, stream,
                        rows, perm, out, n_out, n_rows, D);
   else

@@ -6,6 +6,7 @@
 // Grid: one workgroup per (n, h) row; threads sweep (w, c) with bf16x8
 // vector accesses when C % 8 == 0.
 #include "common.h"
+#include "pool.h"
 
 namespace {
 

@@ -5,6 +5,7 @@
 // class dimension (10 for mnist, up to 4096 supported) is reduced with
 // wave shuffles — no LDS round trip, no separate log-softmax pass.
 #include "common.h"
+#include "softmax_xent.h"
 #include "mlp_head.h"
 
 namespace {

@@ -19,7 +19,7 @@ struct SparseHp {
   float bc1, bc2;       // Adam bias corrections (from step)
 };
 
-long sparse_scratch_rows(long n);
+// scratch: fp32 [run_scratch_rows(n), D] (run_sum.h), null when 0 rows.
 void launch_sparse_apply(int opt, float* table, const long* sorted,
                          const long* perm, const void* grads, bool g_bf16,
                          float* scratch, float* s1, float* s2, bf16_t* shadow,

@@ -22,12 +22,12 @@
 //     window of 64 sorted positions (one per lane), ballots the run
 //     heads among them and processes those; grids are sized from n.
 //     A long run starting at sorted position s owns the scratch slots
-//     s/256 + k (k = chunk index): runs are disjoint position ranges
-//     longer than CHUNK = 2*256, so slots never collide and n/256 + 1
-//     slots always suffice.
-//   * D % 4 == 0: rows are 16-byte aligned -> f32x4 / bf16x4 accesses,
-//     lanes on contiguous columns. Otherwise a scalar path (a vector
-//     access on an odd-D row would be misaligned).
+//     s/256 + k (k = chunk index): the slot scheme of run_sum.h.
+//   * a lane owns VEC consecutive columns per step (ld_vec / st_vec of
+//     tile.h): f32x4 / bf16x4 accesses and 256 columns per step when
+//     D % 4 == 0 and the bases are 16-byte aligned (VEC == 4); otherwise
+//     one column per lane and 64 per step (a vector access on an odd-D
+//     row would be misaligned).
 //   * ids outside [0, V) are ignored (they sort to the ends and are
 //     never heads).
 //   * bag mode (pooled push): grads holds one row per CSR bag; position i
@@ -39,61 +39,12 @@
 #include "common.h"
 
 #include "bag.h"
+#include "run_sum.h"
 #include "sparse_apply.h"
 
 namespace {
 
-constexpr int CHUNK = 512;     // contributions one wave sums
-constexpr int SLOT_DIV = 256;  // scratch slot of a long run = start/256 + k
 constexpr int WAVES = 4;       // waves (64-position windows) per block
-
-template <int VEC>
-DEVINL void ld_f32(const float* __restrict__ p, float (&o)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *(const f32x4*)p;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = t[j];
-  } else {
-    o[0] = p[0];
-  }
-}
-
-template <int VEC>
-DEVINL void st_f32(float* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    f32x4 t;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) t[j] = v[j];
-    *(f32x4*)p = t;
-  } else {
-    p[0] = v[0];
-  }
-}
-
-template <int VEC>
-DEVINL void st_bf16(bf16_t* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    bf16x4 t;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) t[j] = (__bf16)v[j];
-    *(bf16x4*)(__bf16*)p = t;
-  } else {
-    p[0] = f2bf(v[0]);
-  }
-}
-
-template <typename G, int VEC>
-DEVINL void ld_grad(const G* __restrict__ p, float (&o)[VEC]) {
-  if constexpr (sizeof(G) == 4) {
-    ld_f32<VEC>((const float*)p, o);
-  } else if constexpr (VEC == 4) {
-    const bf16x4 t = *(const bf16x4*)(const __bf16*)p;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = (float)t[j];
-  } else {
-    o[0] = bf2f(*(const bf16_t*)p);
-  }
-}
 
 // Bag mode's per-position indirection: position i of the push reads bag
 // gradient row bag_of[i], scaled by coef[i].
@@ -108,7 +59,7 @@ DEVINL const BagIdx& bag_idx(const BagIdx& b) { return b; }
 // [pos, pos+cap) whose sorted id equals id, in position order. The wave
 // reads the index 64 positions at a time (one per lane) and broadcasts
 // each source row; 4 row loads are kept in flight. All 64 lanes must
-// call this (ballot/shuffle); `active` lanes own columns.
+// call this (ballot/shuffle); `active` lanes own the VEC columns at col.
 // Bag mode (one trailing BagIdx): the term of position i = perm[j] is
 // coef[i] * grads[bag_of[i]] instead.
 template <typename G, int VEC, typename... BagP>
@@ -143,10 +94,10 @@ DEVINL void sum_run(const long* __restrict__ sorted,
       }
       if (active) {
         float v0[VEC], v1[VEC], v2[VEC], v3[VEC];
-        ld_grad<G, VEC>(grads + r0 * D + col, v0);
-        ld_grad<G, VEC>(grads + r1 * D + col, v1);
-        ld_grad<G, VEC>(grads + r2 * D + col, v2);
-        ld_grad<G, VEC>(grads + r3 * D + col, v3);
+        ld_vec<G, VEC>(grads + r0 * D + col, v0);
+        ld_vec<G, VEC>(grads + r1 * D + col, v1);
+        ld_vec<G, VEC>(grads + r2 * D + col, v2);
+        ld_vec<G, VEC>(grads + r3 * D + col, v3);
         if constexpr (BAG) {
 #pragma unroll
           for (int e = 0; e < VEC; ++e)
@@ -165,7 +116,7 @@ DEVINL void sum_run(const long* __restrict__ sorted,
       if constexpr (BAG) f = __shfl(cf, k);
       if (active) {
         float v[VEC];
-        ld_grad<G, VEC>(grads + r * D + col, v);
+        ld_vec<G, VEC>(grads + r * D + col, v);
         if constexpr (BAG) {
 #pragma unroll
           for (int e = 0; e < VEC; ++e) acc[e] += f * v[e];
@@ -250,7 +201,7 @@ __global__ __launch_bounds__(WAVES * WAVE) void sparse_partial_kernel(
       for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
       sum_run<G, VEC>(sorted, perm, grads, n, pos, CHUNK, id, D, col, active,
                       lane, acc, bagp...);
-      if (active) st_f32<VEC>(scratch + slot * D + col, acc);
+      if (active) st_vec<float, VEC>(scratch + slot * D + col, acc);
     }
   }
 }
@@ -285,23 +236,23 @@ __global__ __launch_bounds__(WAVES * WAVE) void sparse_apply_kernel(
       // row state first: independent of the index walk below
       float p[VEC], a[VEC], c[VEC];
       if (active) {
-        ld_f32<VEC>(table + off, p);
-        if (OPT >= SPARSE_SGD_MOM) ld_f32<VEC>(s1 + off, a);
-        if (OPT == SPARSE_ADAM) ld_f32<VEC>(s2 + off, c);
+        ld_vec<float, VEC>(table + off, p);
+        if (OPT >= SPARSE_SGD_MOM) ld_vec<float, VEC>(s1 + off, a);
+        if (OPT == SPARSE_ADAM) ld_vec<float, VEC>(s2 + off, c);
       }
       float g[VEC];
 #pragma unroll
       for (int e = 0; e < VEC; ++e) g[e] = 0.f;
       if (!is_long) {
-        sum_run<G, VEC>(sorted, perm, grads, n, pos, CHUNK, id, D, col,
-                        active, lane, g, bagp...);
+        sum_run<G, VEC>(sorted, perm, grads, n, pos, CHUNK, id, D, col, active,
+                        lane, g, bagp...);
       } else {
         // partial sums of pass 1, added in chunk order
         long slot = pos / SLOT_DIV;
         for (long q = pos; q < n && sorted[q] == id; q += CHUNK, ++slot) {
           if (active) {
             float v[VEC];
-            ld_f32<VEC>(scratch + slot * D + col, v);
+            ld_vec<float, VEC>(scratch + slot * D + col, v);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) g[e] += v[e];
           }
@@ -311,10 +262,10 @@ __global__ __launch_bounds__(WAVES * WAVE) void sparse_apply_kernel(
 #pragma unroll
         for (int e = 0; e < VEC; ++e)
           apply_elem<OPT>(p[e], a[e], c[e], g[e], hp);
-        st_f32<VEC>(table + off, p);
-        if (OPT >= SPARSE_SGD_MOM) st_f32<VEC>(s1 + off, a);
-        if (OPT == SPARSE_ADAM) st_f32<VEC>(s2 + off, c);
-        if (shadow != nullptr) st_bf16<VEC>(shadow + off, p);
+        st_vec<float, VEC>(table + off, p);
+        if (OPT >= SPARSE_SGD_MOM) st_vec<float, VEC>(s1 + off, a);
+        if (OPT == SPARSE_ADAM) st_vec<float, VEC>(s2 + off, c);
+        if (shadow != nullptr) st_vec<bf16_t, VEC>(shadow + off, p);
       }
     }
   }
@@ -370,12 +321,7 @@ void launch_any(int opt, float* table, const long* sorted, const long* perm,
                 const void* grads, bool g_bf16, float* scratch, float* s1,
                 float* s2, bf16_t* shadow, long n, int D, long V,
                 const SparseHp& hp, hipStream_t stream, BagP... bagp) {
-  // vector path needs 16-byte aligned rows: D % 4 == 0 and aligned bases
-  // (a view at a storage offset can break the latter)
-  const uintptr_t bases = (uintptr_t)table | (uintptr_t)grads |
-                          (uintptr_t)scratch | (uintptr_t)s1 |
-                          (uintptr_t)s2 | (uintptr_t)shadow;
-  const bool vec = (D % 4) == 0 && (bases % 16) == 0;
+  const bool vec = tile_vec4(D, table, grads, scratch, s1, s2, shadow);
   if (g_bf16) {
     if (vec) launch_typed<bf16_t, 4>(opt, table, sorted, perm,
                                      (const bf16_t*)grads, scratch, s1, s2,
@@ -395,12 +341,8 @@ void launch_any(int opt, float* table, const long* sorted, const long* perm,
 
 }  // namespace
 
-long sparse_scratch_rows(long n) {
-  return n > CHUNK ? n / SLOT_DIV + 1 : 0;
-}
-
 // sorted/perm: the stable sort of the ids and its permutation (n > 0).
-// scratch: fp32 [sparse_scratch_rows(n), D] (may be null when 0 rows).
+// scratch: fp32 [run_scratch_rows(n), D] (may be null when 0 rows).
 void launch_sparse_apply(int opt, float* table, const long* sorted,
                          const long* perm, const void* grads, bool g_bf16,
                          float* scratch, float* s1, float* s2, bf16_t* shadow,

@@ -114,7 +114,73 @@ _HAS_WEIGHTS = 2                # flags bit 1
 _OUT_F32 = 4                    # flags bit 2 (pooled pull: fp32 answer)
 
 
-class EmbeddingTable(object):
+class _SparseOptimizer(object):
+    """The optimizer side of a table, shared by ``EmbeddingTable`` and
+    ``HashedEmbeddingTable``: names and hyper-parameters, which state
+    tensors they need, the fused apply over ``master`` / ``shadow`` /
+    ``state`` / ``step``, and the checkpoint compatibility check."""
+
+    _HPARAMS = {
+        "sgd": {"momentum": 0.0, "weight_decay": 0.0},
+        "adagrad": {"eps": 1e-10, "weight_decay": 0.0},
+        "adam": {"beta1": 0.9, "beta2": 0.999, "eps": 1e-8,
+                 "weight_decay": 0.0},
+    }
+    _STATE = {"sgd": (), "adagrad": ("accum",),
+              "adam": ("exp_avg", "exp_avg_sq")}
+
+    def _init_optimizer(self, optimizer, hparams):
+        """Validates; sets optimizer, hparams and step = 0. Returns the
+        names of the state tensors the table has to allocate."""
+        if optimizer not in self._HPARAMS:
+            raise ValueError("unknown sparse optimizer %r (have %s)"
+                             % (optimizer, sorted(self._HPARAMS)))
+        hp = dict(self._HPARAMS[optimizer])
+        for k, v in hparams.items():
+            if k not in hp:
+                raise ValueError("optimizer %r has no hyper-parameter %r"
+                                 % (optimizer, k))
+            hp[k] = v
+        self.optimizer = optimizer
+        self.hparams = hp
+        self.step = 0
+        if optimizer == "sgd" and hp["momentum"]:
+            return ("momentum_buf",)
+        return self._STATE[optimizer]
+
+    def _push_fused(self, ids, grads, lr, **bag):
+        """bag: offsets/weights/combiner of a pooled push (grads [B,D])."""
+        hp, st = self.hparams, self.state
+        self.step += 1
+        if self.optimizer == "sgd":
+            ops.sparse_sgd(self.master, ids, grads, lr,
+                           momentum=hp["momentum"],
+                           momentum_buf=st.get("momentum_buf"),
+                           weight_decay=hp["weight_decay"],
+                           bf16_out=self.shadow, **bag)
+        elif self.optimizer == "adagrad":
+            ops.sparse_adagrad(self.master, ids, grads, st["accum"], lr,
+                               eps=hp["eps"],
+                               weight_decay=hp["weight_decay"],
+                               bf16_out=self.shadow, **bag)
+        else:
+            ops.sparse_adam(self.master, ids, grads, st["exp_avg"],
+                            st["exp_avg_sq"], self.step, lr,
+                            beta1=hp["beta1"], beta2=hp["beta2"],
+                            eps=hp["eps"], weight_decay=hp["weight_decay"],
+                            bf16_out=self.shadow, **bag)
+
+    def _check_state_dict(self, sd):
+        if sd["optimizer"] != self.optimizer:
+            raise ValueError("checkpoint is for optimizer %r, table uses %r"
+                             % (sd["optimizer"], self.optimizer))
+        if set(sd["state"]) != set(self.state):
+            raise ValueError("checkpoint state %s does not match table "
+                             "state %s" % (sorted(sd["state"]),
+                                           sorted(self.state)))
+
+
+class EmbeddingTable(_SparseOptimizer):
     """One PS-resident table: fp32 master + bf16 pull shadow (+ fp32
     optimizer state rows).
 
@@ -128,44 +194,22 @@ class EmbeddingTable(object):
     opts it into the fused sparse-apply kernel; every other
     configuration always uses the fused kernel (``ops.sparse_*``)."""
 
-    _HPARAMS = {
-        "sgd": {"momentum": 0.0, "weight_decay": 0.0},
-        "adagrad": {"eps": 1e-10, "weight_decay": 0.0},
-        "adam": {"beta1": 0.9, "beta2": 0.999, "eps": 1e-8,
-                 "weight_decay": 0.0},
-    }
-    _STATE = {"sgd": (), "adagrad": ("accum",),
-              "adam": ("exp_avg", "exp_avg_sq")}
-
     def __init__(self, name, rows, dim, device="cpu", lr=0.01, seed=0,
                  optimizer="sgd", fused_apply=False, **hparams):
-        if optimizer not in self._HPARAMS:
-            raise ValueError("unknown sparse optimizer %r (have %s)"
-                             % (optimizer, sorted(self._HPARAMS)))
-        hp = dict(self._HPARAMS[optimizer])
-        for k, v in hparams.items():
-            if k not in hp:
-                raise ValueError("optimizer %r has no hyper-parameter %r"
-                                 % (optimizer, k))
-            hp[k] = v
+        names = self._init_optimizer(optimizer, hparams)
         self.name = name
         self.rows = rows
         self.dim = dim
         self.lr = lr
-        self.optimizer = optimizer
-        self.hparams = hp
-        self.step = 0
         self.device = torch.device(device)
         self.master = self._init_rows(rows, dim, seed).to(self.device)
         self.shadow = self.master.to(torch.bfloat16)
-        names = self._STATE[optimizer]
-        if optimizer == "sgd" and hp["momentum"]:
-            names = ("momentum_buf",)
         self.state = {k: torch.zeros(rows, dim, device=self.device)
                       for k in names}
         # the scatter-add path can only add -lr*g: anything else is fused
         self.fused = bool(fused_apply or optimizer != "sgd"
-                          or hp["momentum"] or hp["weight_decay"])
+                          or self.hparams["momentum"]
+                          or self.hparams["weight_decay"])
         self.lock = threading.Lock()
 
     @staticmethod
@@ -211,28 +255,6 @@ class EmbeddingTable(object):
             self.shadow.index_copy_(
                 0, uniq, self.master.index_select(0, uniq).to(torch.bfloat16))
 
-    def _push_fused(self, ids, grads, lr, **bag):
-        """bag: offsets/weights/combiner of a pooled push (grads [B,D])."""
-        hp, st = self.hparams, self.state
-        self.step += 1
-        if self.optimizer == "sgd":
-            ops.sparse_sgd(self.master, ids, grads, lr,
-                           momentum=hp["momentum"],
-                           momentum_buf=st.get("momentum_buf"),
-                           weight_decay=hp["weight_decay"],
-                           bf16_out=self.shadow, **bag)
-        elif self.optimizer == "adagrad":
-            ops.sparse_adagrad(self.master, ids, grads, st["accum"], lr,
-                               eps=hp["eps"],
-                               weight_decay=hp["weight_decay"],
-                               bf16_out=self.shadow, **bag)
-        else:
-            ops.sparse_adam(self.master, ids, grads, st["exp_avg"],
-                            st["exp_avg_sq"], self.step, lr,
-                            beta1=hp["beta1"], beta2=hp["beta2"],
-                            eps=hp["eps"], weight_decay=hp["weight_decay"],
-                            bf16_out=self.shadow, **bag)
-
     def pull_pooled(self, ids, offsets, weights=None, combiner="sum",
                     out_dtype=None):
         """bf16 [B,D] pooled rows from the shadow: bag b (positions
@@ -274,13 +296,7 @@ class EmbeddingTable(object):
     def load_state_dict(self, sd):
         """Copy INTO the existing buffers (callers may hold views) and
         rebuild the bf16 shadow from the restored master."""
-        if sd["optimizer"] != self.optimizer:
-            raise ValueError("checkpoint is for optimizer %r, table uses %r"
-                             % (sd["optimizer"], self.optimizer))
-        if set(sd["state"]) != set(self.state):
-            raise ValueError("checkpoint state %s does not match table "
-                             "state %s" % (sorted(sd["state"]),
-                                           sorted(self.state)))
+        self._check_state_dict(sd)
         with self.lock:
             self.master.copy_(sd["master"])
             for k, v in sd["state"].items():
@@ -476,7 +492,7 @@ class ShardedEmbeddingTable(object):
             t.load_state_dict(shard_sd)
 
 
-class HashedEmbeddingTable(object):
+class HashedEmbeddingTable(_SparseOptimizer):
     """A PS-resident table addressed by arbitrary int64 KEYS: a key gets the
     next free row the first time a request names it (``ops.HashIndex``,
     insert on first use), up to ``capacity`` rows.
@@ -528,10 +544,6 @@ class HashedEmbeddingTable(object):
     * ``SparseWorkerClient(coalesce=True)`` works as is:
       ``ops.coalesce_ids`` never looks at the id range."""
 
-    _HPARAMS = EmbeddingTable._HPARAMS
-    _STATE = EmbeddingTable._STATE
-    _push_fused = EmbeddingTable._push_fused    # same fields, same applies
-
     def __init__(self, name, dim, capacity, device="cpu", lr=0.01, seed=0,
                  optimizer="sgd", insert_on_pull=True, key_mul=1, key_add=0,
                  track_use=False, max_idle=None, evict_every=None,
@@ -549,30 +561,15 @@ class HashedEmbeddingTable(object):
             raise ValueError("need max_idle >= 1 and evict_every >= 1, got "
                              "max_idle=%r, evict_every=%r"
                              % (max_idle, evict_every))
-        if optimizer not in self._HPARAMS:
-            raise ValueError("unknown sparse optimizer %r (have %s)"
-                             % (optimizer, sorted(self._HPARAMS)))
-        hp = dict(self._HPARAMS[optimizer])
-        for k, v in hparams.items():
-            if k not in hp:
-                raise ValueError("optimizer %r has no hyper-parameter %r"
-                                 % (optimizer, k))
-            hp[k] = v
+        self._state_names = self._init_optimizer(optimizer, hparams)
         self.name = name
         self.dim = dim
         self.lr = lr
         self.seed = int(seed)
         self.key_mul, self.key_add = int(key_mul), int(key_add)
-        self.optimizer = optimizer
-        self.hparams = hp
         self.insert_on_pull = bool(insert_on_pull)
-        self.step = 0
         self.device = torch.device(device)
         self.index = ops.HashIndex(capacity, self.device)
-        names = self._STATE[optimizer]
-        if optimizer == "sgd" and hp["momentum"]:
-            names = ("momentum_buf",)
-        self._state_names = names
         self._alloc(self.index.capacity)
         self.track_use = bool(track_use or max_idle is not None)
         self.max_idle = None if max_idle is None else int(max_idle)
@@ -742,16 +739,15 @@ class HashedEmbeddingTable(object):
         place that syncs: the counters live on the device and nothing else
         reads them."""
         with self.lock:
+            counters = [self.index.size, self.index.dropped]
             if self.track_use:
-                size, dropped, evicted = torch.cat(
-                    [self.index.size, self.index.dropped,
-                     self.index.evicted]).tolist()
-                return {"size": size, "dropped": dropped,
-                        "capacity": self.index.capacity, "evicted": evicted}
-            size, dropped = torch.cat(
-                [self.index.size, self.index.dropped]).tolist()
-            return {"size": size, "dropped": dropped,
-                    "capacity": self.index.capacity}
+                counters.append(self.index.evicted)
+            size, dropped, *evicted = torch.cat(counters).tolist()
+            out = {"size": size, "dropped": dropped,
+                   "capacity": self.index.capacity}
+            if self.track_use:
+                out["evicted"] = evicted[0]
+            return out
 
     def reserve(self, capacity):
         """Grow to ``capacity`` rows (explicit; nothing grows by itself):
@@ -799,13 +795,7 @@ class HashedEmbeddingTable(object):
         the keys keep their rows, index and shadow are rebuilt, and the
         table takes the checkpoint's seed — it then trains on exactly as
         the saved one would have."""
-        if sd["optimizer"] != self.optimizer:
-            raise ValueError("checkpoint is for optimizer %r, table uses %r"
-                             % (sd["optimizer"], self.optimizer))
-        if set(sd["state"]) != set(self.state):
-            raise ValueError("checkpoint state %s does not match table "
-                             "state %s" % (sorted(sd["state"]),
-                                           sorted(self.state)))
+        self._check_state_dict(sd)
         n = sd["keys"].numel()
         if n > self.index.capacity:
             raise ValueError("checkpoint holds %d keys, table %r has "
@@ -833,7 +823,8 @@ def make_sparse_pair_groups(ps_ranks, worker_ranks):
 
 class _Posted(object):
     """Non-blocking sends and receives posted on several channels and
-    awaited together (the pattern of ``pull_many``)."""
+    awaited together: ``pull_many`` / ``push_many`` and every request to
+    a row-sharded table."""
 
     def __init__(self):
         self.sends, self.keep, self.recvs = [], [], []
@@ -923,7 +914,6 @@ class SparseWorkerClient(object):
                                  % (name, name))
             ops.shard_rows(self.rows[name], len(h), 0,
                            self._strategy(name))    # validates
-        import torch.distributed as dist
         self._hdr_dev = self.device if dist.get_backend() == "nccl" \
             else torch.device("cpu")
 
@@ -1165,37 +1155,19 @@ class SparseWorkerClient(object):
                  for (name, ids), cu in zip(reqs, cos)], coalesce=False)
             return [r if cu is None else ops.embedding_gather(r, cu[0].inverse)
                     for r, cu in zip(rows, cos)]
-        keep, works = [], []
-        recv = []
+        post, recv = _Posted(), []
         for name, ids in reqs:
             c = self._chan(name)
             ids = ids.to(self.device)
-            for t in (self._hdr(ids.numel(), self._tidx(name)), ids):
-                w, s = c.isend(t)
-                works.append(w)
-                keep.append(s)
-            rows = torch.empty(ids.numel(), self.dims[name],
-                               dtype=torch.bfloat16, device=self.device)
-            recv.append((c, rows))
-        rworks = []
-        for c, rows in recv:
-            if c.device_only:
-                rworks.append((dist.irecv(rows, src=c.peer, group=c.group),
-                               rows, rows))
-            else:
-                buf = rows if rows.device.type == "cpu" else \
-                    torch.empty(rows.shape, dtype=rows.dtype, device="cpu")
-                rworks.append((dist.irecv(buf, src=c.peer, group=c.group),
-                               buf, rows))
-        for w in works:
-            w.wait()
-        out = []
-        for w, buf, rows in rworks:
-            w.wait()
-            if buf is not rows:
-                rows.copy_(buf)
-            out.append(rows)
-        return out
+            post.send(c, self._hdr(ids.numel(), self._tidx(name)))
+            post.send(c, ids)
+            recv.append((c, torch.empty(ids.numel(), self.dims[name],
+                                        dtype=torch.bfloat16,
+                                        device=self.device)))
+        for c, rows in recv:    # every send is posted before any receive
+            post.recv(c, rows)
+        post.wait()
+        return [rows for _, rows in recv]
 
     def push_many(self, reqs, coalesce=None):
         """Concurrent pushes: [(name, ids, grads)] — all sends issued
@@ -1207,17 +1179,14 @@ class SparseWorkerClient(object):
                  (name, cu[0].uniq[:cu[1]],
                   self._coalesce_grads(name, cu[0], cu[1], g))
                  for (name, ids, g), cu in zip(reqs, cos)], coalesce=False)
-        keep, works = [], []
+        post = _Posted()
         for name, ids, grads in reqs:
             c = self._chan(name)
             ids = ids.to(self.device)
-            for t in (self._hdr(-ids.numel(), self._tidx(name)), ids,
-                      grads.to(device=self.device, dtype=torch.bfloat16)):
-                w, s = c.isend(t)
-                works.append(w)
-                keep.append(s)
-        for w in works:
-            w.wait()
+            post.send(c, self._hdr(-ids.numel(), self._tidx(name)))
+            post.send(c, ids)
+            post.send(c, grads.to(device=self.device, dtype=torch.bfloat16))
+        post.wait()
 
     def done_all(self):
         """One shutdown marker per PS RANK (its serving loop drops this
@@ -1261,25 +1230,19 @@ class SparsePSServer(object):
         if word >> _KIND_SHIFT == _KIND_POOLED:
             self._handle_pooled(c, hdr, table, count)
             return True
-        if word >> _KIND_SHIFT == _KIND_ROWS:
-            self._handle_rows(c, table, count)
-            return True
-        ids = c.recv_new((abs(count),), torch.int64, table.device)
-        if count > 0:
-            c.send(table.pull(ids))
-        else:
-            grads = c.recv_new((abs(count), table.dim), torch.bfloat16,
-                               table.device)
-            table.push(ids, grads)
+        # row requests: kind 2 counts +-(n + 1), kind 0 +-n (never n == 0)
+        kind2 = word >> _KIND_SHIFT == _KIND_ROWS
+        self._handle_rows(c, table, abs(count) - (1 if kind2 else 0),
+                          count > 0)
         return True
 
-    def _handle_rows(self, c, table, count):
-        """One kind-2 row request (count = +-(n + 1)): a push of zero rows
+    def _handle_rows(self, c, table, n, pull):
+        """One row request of n ids: a push of zero rows (kind 2 only)
         still reaches ``table.push``, which advances ``step``."""
-        n, dev = abs(count) - 1, table.device
+        dev = table.device
         ids = c.recv_new((n,), torch.int64, dev) if n else \
             torch.empty(0, dtype=torch.int64, device=dev)
-        if count > 0:
+        if pull:
             if n:       # no zero-size messages
                 c.send(table.pull(ids))
             return
@@ -1310,7 +1273,6 @@ class SparsePSServer(object):
             table.push_pooled(ids, offsets, grads, weights, combiner)
 
     def serve(self):
-        import torch.distributed as dist
         if dist.get_backend() == "nccl":
             self._serve_polling()
         else:
