@@ -709,20 +709,73 @@ DEVINL void small_cs_reduce(const float* csp, float* csw, int lane) {
 // (4 each, straight from the LDS partials) — the wave0-only form
 // serialized the master-read/store latency on one wave per block
 // and measured SLOWER than the separate wide sgd_kernel
-DEVINL void small_sgd_w1b1(const SmallSgd& sg, const float (*red)[64 * 16],
-                           const float (*csred)[32], bool cs, int m0, int n0,
-                           int M, int N, int ldc, int w, int lane) {
+//
+// Two halves. small_sgd_fetch reads the masters this lane will update
+// and is called at the TOP of the kernel: no master depends on anything
+// the launch computes, each element is read and written by exactly one
+// thread per launch, and stream order covers the previous step's store
+// — so the read rides under the kernel's other loads instead of being a
+// dependent round trip after the barrier (the one-function form
+// compiled to load / wait / store per element, each load held behind
+// the previous store because the pointers may alias). Lanes outside
+// the tile read element 0 and drop the value: unconditional loads keep
+// the compiler from fencing each one in a branch of its own.
+// small_sgd_commit is what is left after the barrier: LDS reads,
+// arithmetic and stores.
+struct SmallSgdPre {
+  float w[4];
+  float b;
+};
+
+// Explicit s_waitcnt (gfx9 operand: vmcnt [3:0] and [15:14], expcnt
+// [6:4], lgkmcnt [11:8]; all ones = no wait on that counter). The
+// compiler's own wait insertion sees it and drops the waits it covers.
+// Used where values fetched long ago are consumed across divergent
+// store blocks: the compiler can only prove a small distance to such a
+// load there and emits vmcnt(3), (2), (1), (0) between the stores —
+// stores count on vmcnt too, so each block then waits for the stores
+// before it to be acknowledged. One vmcnt(0) ahead of the first store,
+// when nothing is in flight any more, costs nothing and removes them.
+DEVINL void wait_vm0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+DEVINL void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
+
+DEVINL int small_sgd_row(int m0, int w, int u, int lane) {
+  const int v = w * 4 + u;
+  return m0 + ((v >> 2) << 3) + ((lane >> 5) << 2) + (v & 3);
+}
+
+DEVINL void small_sgd_fetch(const SmallSgd& sg, SmallSgdPre& pre, bool cs,
+                            int m0, int n0, int M, int N, int ldc, int w,
+                            int lane) {
+  const int n = n0 + (lane & 31);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int m = small_sgd_row(m0, w, u, lane);
+    const long idx = (n < N && m < M) ? (long)m * ldc + n : 0;
+    pre.w[u] = sg.pmw[idx];
+  }
+  pre.b = 0.f;
+  if (cs && blockIdx.x == 0 && sg.pmb != nullptr) {
+    const int nn = n0 + (lane & 31);
+    pre.b = sg.pmb[nn < N ? nn : 0];
+  }
+}
+
+DEVINL void small_sgd_commit(const SmallSgd& sg, const SmallSgdPre& pre,
+                             const float (*red)[64 * 16],
+                             const float (*csred)[32], bool cs, int m0,
+                             int n0, int M, int N, int ldc, int w, int lane) {
   const int n = n0 + (lane & 31);
   if (n < N) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int v = w * 4 + u;
-      const int m = m0 + ((v >> 2) << 3) + ((lane >> 5) << 2) + (v & 3);
+      const int m = small_sgd_row(m0, w, u, lane);
       if (m >= M) continue;
       const float x = red[0][lane * 16 + v] + red[1][lane * 16 + v] +
                       red[2][lane * 16 + v] + red[3][lane * 16 + v];
       const long idx = (long)m * ldc + n;
-      const float pv = sg.pmw[idx] - sg.lr * x;
+      const float pv = pre.w[u] - sg.lr * x;
       sg.pmw[idx] = pv;
       sg.psw[idx] = f2bf(pv);
     }
@@ -732,7 +785,7 @@ DEVINL void small_sgd_w1b1(const SmallSgd& sg, const float (*red)[64 * 16],
     if (nn < N && sg.pmb != nullptr) {
       const float sv = csred[0][lane] + csred[1][lane] + csred[2][lane] +
                        csred[3][lane];
-      const float pv = sg.pmb[nn] - sg.lr * sv;
+      const float pv = pre.b - sg.lr * sv;
       sg.pmb[nn] = pv;
       sg.psb[nn] = f2bf(pv);
     }
@@ -814,6 +867,10 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
   f32x4 acc[4] = {};
   float csp[16] = {};
   bf16x8 ra0, ra1, rb0, rb1;        // in-flight chunk (load -> commit)
+  // APPLY: this lane's W1/b1 masters, in flight under the whole k-loop
+  SmallSgdPre pre = {};
+  if (sg.pmw != nullptr)
+    small_sgd_fetch(sg, pre, CS, m0, n0, M, N, ldc, w, lane);
 
   // load: global reads into REGISTERS (vector when the row allows —
   // guarded scalar loads serialized the first cut at 2x the split-K
@@ -918,6 +975,7 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
   for (int v = 0; v < 16; ++v) red[w][lane * 16 + v] = ((float*)acc)[v];
   if (CS && blockIdx.x == 0) small_cs_reduce(csp, csred[w], lane);
   __syncthreads();
+  wait_vm0();   // the prefetched masters landed a k-loop ago
   if (sg.pm2w != nullptr && w == 1 && blockIdx.x == 0 && blockIdx.y == 0) {
     // classifier apply: ~1k elems on one idle wave; runs strictly
     // after the head kernel wrote g2w/g2b (stream order), and nothing
@@ -927,17 +985,31 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
     // trips on this single wave and cost MORE than the sgd_kernel it
     // replaced. Buffers are 256-elem-aligned flat-store slices, so
     // the f32x4/bf16x4 accesses are aligned.
+    // The first pass of the two scalar loops below (the n2w % 4 tail
+    // and the bias) is loaded here as well, ahead of every store: a
+    // load issued after a store to a pointer it may alias waits for it.
     const int nv = sg.n2w >> 2;
-    f32x4 mv[4];
-    bf16x4 gv[4];
+    // Lanes beyond a range read its element 0 and drop the value (a
+    // load guarded per lane sits in a branch of its own, and the
+    // compiler waited for the loads in flight inside each of them).
+    f32x4 mv[4] = {};
+    bf16x4 gv[4] = {};
+    if (nv > 0) {
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = lane + u * 64;
-      if (i < nv) {
-        gv[u] = ((const bf16x4*)sg.g2w)[i];
-        mv[u] = ((const f32x4*)sg.pm2w)[i];
+      for (int u = 0; u < 4; ++u) {
+        const int i = lane + u * 64;
+        gv[u] = ((const bf16x4*)sg.g2w)[i < nv ? i : 0];
+        mv[u] = ((const f32x4*)sg.pm2w)[i < nv ? i : 0];
       }
     }
+    const int it = (nv << 2) + lane;
+    const int itc = it < sg.n2w ? it : 0;
+    const int ibc = lane < sg.n2b ? lane : 0;
+    const float mt = sg.pm2w[itc];
+    const bf16_t gt = sg.g2w[itc];
+    const float mb = sg.pm2b[ibc];
+    const bf16_t gb = sg.g2b[ibc];
+    wait_vm0();   // the one round trip of this wave
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int i = lane + u * 64;
@@ -966,19 +1038,24 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
       ((f32x4*)sg.pm2w)[i] = pv;
       ((bf16x4*)sg.ps2w)[i] = sv;
     }
-    for (int i = (nv << 2) + lane; i < sg.n2w; i += 64) {   // n2w % 4
-      const float pv = sg.pm2w[i] - sg.lr * bf2f(sg.g2w[i]);
-      sg.pm2w[i] = pv;
-      sg.ps2w[i] = f2bf(pv);
+    if (it < sg.n2w) {                                      // n2w % 4
+      const float pv = mt - sg.lr * bf2f(gt);
+      sg.pm2w[it] = pv;
+      sg.ps2w[it] = f2bf(pv);
     }
-    for (int i = lane; i < sg.n2b; i += 64) {
+    if (lane < sg.n2b) {
+      const float pv = mb - sg.lr * bf2f(gb);
+      sg.pm2b[lane] = pv;
+      sg.ps2b[lane] = f2bf(pv);
+    }
+    for (int i = lane + 64; i < sg.n2b; i += 64) {          // > 64 classes
       const float pv = sg.pm2b[i] - sg.lr * bf2f(sg.g2b[i]);
       sg.pm2b[i] = pv;
       sg.ps2b[i] = f2bf(pv);
     }
   }
   if (sg.pmw != nullptr) {
-    small_sgd_w1b1(sg, red, csred, CS, m0, n0, M, N, ldc, w, lane);
+    small_sgd_commit(sg, pre, red, csred, CS, m0, n0, M, N, ldc, w, lane);
     return;
   }
   if (w != 0) return;
@@ -1039,7 +1116,10 @@ struct HeadTail {
   int C;
 };
 
-template <bool APPLY, bool GF32>
+// SNAP (APPLY only): w2/b2 are the snapshot and the classifier block is
+// fixed, known at entry — it fetches its W2/b2 masters with everything
+// else. !SNAP: the ticket decides, so they are fetched after it.
+template <bool APPLY, bool GF32, bool SNAP>
 __global__ __launch_bounds__(256)
 void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
                           void* __restrict__ Cout,
@@ -1072,51 +1152,109 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
   const int kk = lane & 31;
   const int half = lane >> 5;
 
-  // 1. the x chunk (gemm_small's load_a, A half) flies under the head
+  // 1. EVERY global load of the launch, back to back, so the kernel is
+  // one memory round trip deep: the x chunk (gemm_small's load_a, A
+  // half), this wave's 32 rows of h (b64 chunks, two rows per pass), the
+  // classifier (one hidden row per lane), its bias, the labels and —
+  // APPLY — the fp32 masters this lane updates after the barrier.
+  // All of them are unconditional loads from addresses clamped into
+  // the tensor (element 0 where the lane has nothing to read) with the
+  // select and every conversion AFTER the last load: a load guarded by
+  // a lane condition gets a branch of its own, and the compiler drains
+  // the loads in flight (s_waitcnt vmcnt(0)) inside such branches —
+  // the guarded form of this prologue was three round trips, not one.
+  const int gk = ks + kk;
+  const int gm = m0 + half * 16;
+  const bool xvec = (M & 7) == 0;       // rows of x are whole b128 chunks
   bf16x8 ra0 = {}, ra1 = {};
+  // ragged rows: element loads, one whole register each (two bf16
+  // sharing a register would make the second load wait for the first).
+  // Assigned and read only where !xvec — no initializer: zeroing 16
+  // registers on the vector path put counted waits there, for loads
+  // the compiler must assume pending on them.
+  unsigned xs[16];
   {
-    const int gk = ks + kk;
-    const int gm = m0 + half * 16;
-    if (gk < ke) {
-      const __bf16* src = X + (long)gk * M + gm;
-      if ((M & 7) == 0 && gm + 16 <= M) {
-        ra0 = *(const bf16x8*)src;
-        ra1 = *(const bf16x8*)(src + 8);
-      } else {
+    const __bf16* rowp = X + (long)(gk < ke ? gk : 0) * M;
+    if (xvec) {
+      // M % 8 == 0 and gm % 8 == 0: a chunk is whole or absent
+      ra0 = *(const bf16x8*)(rowp + (gm < M ? gm : 0));
+      ra1 = *(const bf16x8*)(rowp + (gm + 8 < M ? gm + 8 : 0));
+    } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if (gm + j < M) ra0[j] = src[j];
-          if (gm + 8 + j < M) ra1[j] = src[8 + j];
-        }
-      }
+      for (int j = 0; j < 16; ++j)
+        xs[j] = ((const unsigned short*)rowp)[gm + j < M ? gm + j : 0];
     }
   }
-  // 2. this wave's 32 rows of h (b64 chunks, two rows per pass; zeros
-  // beyond B and H so the LDS image needs no separate clear), the
-  // classifier (one hidden row per lane), bias and labels — every
-  // global load is issued before the first LDS store waits on one
+  const int hc4 = kk * 4;               // this lane's h columns
   bf16x4 hv[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int id = i * 64 + lane;
-    const int r = ks + (id >> 5);
-    const int c4 = (id & 31) * 4;
-    hv[i] = bf16x4{};
-    if (r < K && c4 < N) hv[i] = *(const bf16x4*)&ht.h[(long)r * N + c4];
+    const int r = ks + 2 * i + half;
+    const long off = (r < K && hc4 < N) ? (long)r * N + hc4 : 0;
+    hv[i] = *(const bf16x4*)&ht.h[off];
   }
   __bf16 wv[2][CP];
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int hr = lane + q * 64;
 #pragma unroll
-    for (int c = 0; c < CP; ++c) {
-      wv[q][c] = (__bf16)0.f;
-      if (hr < N && c < C) wv[q][c] = ht.w2[hr * C + c];
+    for (int c = 0; c < CP; ++c)
+      wv[q][c] = ht.w2[(hr < N && c < C) ? hr * C + c : 0];
+  }
+  const bf16_t braw = ht.b2[kk < C ? kk : 0];
+  // the label's low dword is all (int)label keeps; a b64 load's unused
+  // high register was reused at once, behind a vmcnt(0)
+  const int lraw = ((const int*)ht.labels)[2 * (ks + kk < K ? ks + kk : 0)];
+  SmallSgdPre pre = {};
+  float pm2[16] = {};
+  float pm2bv = 0.f;
+  // the block that applies W2/b2 where it is fixed (see below)
+  const bool snap_head =
+      APPLY && SNAP && blockIdx.x == gridDim.x - 1 && blockIdx.y == 0;
+  if (APPLY) {
+    small_sgd_fetch(sg, pre, true, m0, n0, M, N, N, w, lane);
+    if (snap_head) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const int hrow = ks + head_frag_row(v, lane);
+        pm2[v] = sg.pm2w[(kk < C && hrow < N) ? hrow * C + kk : 0];
+      }
+      pm2bv = sg.pm2b[t < C ? t : 0];
     }
   }
-  const float bc = kk < C ? bf2f(ht.b2[kk]) : 0.f;
-  int label = 0;
-  if (lane < 32 && ks + lane < K) label = (int)ht.labels[ks + lane];
+
+  // 2. selects and conversions, then the LDS images (zeros beyond B, H
+  // and C, so none of them needs a separate clear pass over live data)
+  const bf16x4 z4 = {};
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    if (!(ks + 2 * i + half < K && hc4 < N)) hv[i] = z4;
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+#pragma unroll
+    for (int c = 0; c < CP; ++c)
+      if (!(lane + q * 64 < N && c < C)) wv[q][c] = (__bf16)0.f;
+  const float bc = kk < C ? bf2f(braw) : 0.f;
+  const int label = (lane < 32 && ks + lane < K) ? (int)lraw : 0;
+  {
+    const bf16x8 z8x = {};
+    if (xvec) {
+      if (!(gk < ke && gm < M)) ra0 = z8x;
+      if (!(gk < ke && gm + 8 < M)) ra1 = z8x;
+    } else {
+      u32x4 d0, d1;
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (!(gk < ke && gm + j < M)) xs[j] = 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        d0[j] = xs[2 * j] | (xs[2 * j + 1] << 16);
+        d1[j] = xs[8 + 2 * j] | (xs[9 + 2 * j] << 16);
+      }
+      ra0 = __builtin_bit_cast(bf16x8, d0);
+      ra1 = __builtin_bit_cast(bf16x8, d1);
+    }
+  }
 
   {
     const bf16x8 z8 = {};
@@ -1124,22 +1262,25 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
     *(bf16x8*)&wpw[lane * 8] = z8;
   }
 #pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int id = i * 64 + lane;
-    *(bf16x4*)&hs[(ks + (id >> 5)) * HP + (id & 31) * 4] = hv[i];
-  }
+  for (int i = 0; i < 16; ++i)
+    *(bf16x4*)&hs[(ks + 2 * i + half) * HP + hc4] = hv[i];
+  // wtw: column hr of the [c][k] image, all CP classes (wv is zero
+  // beyond C and H — the same zeros the clear put there); wpw: the
+  // lane's whole row of the N tile as two b128 stores
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int hr = lane + q * 64;
-    if (hr < N) {
-      const bool mine = hr >= n0 && hr < n0 + 32;
 #pragma unroll
-      for (int c = 0; c < CP; ++c) {
-        if (c < C) {
-          wtw[c * HP + hr] = wv[q][c];
-          if (mine) wpw[(hr - n0) * CP + c] = wv[q][c];
-        }
+    for (int c = 0; c < CP; ++c) wtw[c * HP + hr] = wv[q][c];
+    if (hr >= n0 && hr < n0 + 32 && hr < N) {
+      bf16x8 lo, hi;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        lo[c] = wv[q][c];
+        hi[c] = wv[q][8 + c];
       }
+      *(bf16x8*)&wpw[(hr - n0) * CP] = lo;
+      *(bf16x8*)&wpw[(hr - n0) * CP + 8] = hi;
     }
   }
 
@@ -1165,14 +1306,22 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
   }
   // 5. dh fragment -> relu mask -> bf16 -> the k-major Bs image, where
   // commit() would have put the loaded dh (zeros beyond B and H)
+  // The 16 mask values do not depend on the MFMA: they are read ahead
+  // of it, in one batch (read inside the loop, each one waited for the
+  // Bs store before it, which might alias it — 16 LDS round trips)
   {
+    const int colh = n0 + kk;
+    __bf16 hm[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v)
+      hm[v] = hs[(ks + head_frag_row(v, lane)) * HP + colh];
     const f32x16v acc =
         head_dh_tile(&dls[(ks + kk) * CP], &wpw[kk * CP], lane);
-    const int colh = n0 + kk;
+    wait_lgkm0();   // hm, under the MFMA: no LDS wait inside the loop
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
       const int rl = head_frag_row(v, lane);
-      const float hval = (float)hs[(ks + rl) * HP + colh];
+      const float hval = (float)hm[v];
       const float m =
           (ks + rl < K && colh < N && hval > 0.f) ? acc[v] : 0.f;
       const bf16_t r = f2bf(m);
@@ -1209,23 +1358,36 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
 #pragma unroll
   for (int v = 0; v < 16; ++v) red[w][lane * 16 + v] = ((float*)acc)[v];
   __syncthreads();
+  wait_vm0();   // the prefetched masters landed a whole head ago
 
   bool head_block;
-  const bool ticketed = APPLY && ht.ticket != nullptr;
+  constexpr bool ticketed = APPLY && !SNAP;   // ht.ticket != null
   if (APPLY) {
     if (ticketed && t == 0)
       tick = __hip_atomic_fetch_add(ht.ticket, 1u, __ATOMIC_ACQ_REL,
                                     __HIP_MEMORY_SCOPE_AGENT);
-    small_sgd_w1b1(sg, red, csred, true, m0, n0, M, N, N, w, lane);
+    small_sgd_commit(sg, pre, red, csred, true, m0, n0, M, N, N, w, lane);
     if (ticketed) {
       __syncthreads();
       head_block = tick == gridDim.x * gridDim.y - 1;
+      if (head_block) {
+        // only now known: the W2/b2 masters, all 17 loads in one batch
+        // (the stores above are to W1/b1, but may alias for all the
+        // compiler knows — the batch waits for them once, not per load)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const int hrow = ks + head_frag_row(v, lane);
+          pm2[v] = sg.pm2w[(kk < C && hrow < N) ? hrow * C + kk : 0];
+        }
+        pm2bv = sg.pm2b[t < C ? t : 0];
+        wait_vm0();
+      }
     } else {
       // w2/b2 are a snapshot the preceding launch took: nobody reads
       // the live shadow here, so a fixed block applies right away, in
       // parallel with the other tiles (the ragged last M tile has the
-      // least W1 work and no b1 apply)
-      head_block = blockIdx.x == gridDim.x - 1 && blockIdx.y == 0;
+      // least W1 work and no b1 apply); its masters came with step 1
+      head_block = snap_head;
     }
   } else {
     if (gridDim.x * gridDim.y >= 32) {
@@ -1307,7 +1469,7 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
           const int idx = hrow * C + kk;
           if (APPLY) {
             // bf16-rounded like the grads the head used to store
-            const float pv = sg.pm2w[idx] - sg.lr * bf2f(f2bf(acc2[v]));
+            const float pv = pm2[v] - sg.lr * bf2f(f2bf(acc2[v]));
             sg.pm2w[idx] = pv;
             sg.ps2w[idx] = f2bf(pv);
           } else if (GF32) {
@@ -1332,7 +1494,7 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
 #pragma unroll
     for (int p2 = 0; p2 < 16; ++p2) s += db2p[t * 16 + p2];
     if (APPLY) {
-      const float pv = sg.pm2b[t] - sg.lr * bf2f(f2bf(s));
+      const float pv = pm2bv - sg.lr * bf2f(f2bf(s));
       sg.pm2b[t] = pv;
       sg.ps2b[t] = f2bf(pv);
     } else if (GF32) {
@@ -1631,15 +1793,22 @@ void launch_mlp_head_tail(const bf16_t* x, const HeadTailArgs* hta,
     sg.pm2w = sga->pm2w; sg.ps2w = (bf16_t*)sga->ps2w;
     sg.pm2b = sga->pm2b; sg.ps2b = (bf16_t*)sga->ps2b;
     sg.lr = sga->lr; sg.n2w = sga->n2w; sg.n2b = sga->n2b;
-    hipLaunchKernelGGL((mlp_head_tail_kernel<true, false>), grid, block, 0,
-                       stream, (const __bf16*)x, ht, nullptr, nullptr, M, H,
-                       B, sg);
+    if (ht.ticket == nullptr)
+      hipLaunchKernelGGL((mlp_head_tail_kernel<true, false, true>), grid,
+                         block, 0, stream, (const __bf16*)x, ht, nullptr,
+                         nullptr, M, H, B, sg);
+    else
+      hipLaunchKernelGGL((mlp_head_tail_kernel<true, false, false>), grid,
+                         block, 0, stream, (const __bf16*)x, ht, nullptr,
+                         nullptr, M, H, B, sg);
   } else if (grads_f32) {
-    hipLaunchKernelGGL((mlp_head_tail_kernel<false, true>), grid, block, 0,
-                       stream, (const __bf16*)x, ht, dw1, db1, M, H, B, sg);
+    hipLaunchKernelGGL((mlp_head_tail_kernel<false, true, false>), grid,
+                       block, 0, stream, (const __bf16*)x, ht, dw1, db1, M, H,
+                       B, sg);
   } else {
-    hipLaunchKernelGGL((mlp_head_tail_kernel<false, false>), grid, block, 0,
-                       stream, (const __bf16*)x, ht, dw1, db1, M, H, B, sg);
+    hipLaunchKernelGGL((mlp_head_tail_kernel<false, false, false>), grid,
+                       block, 0, stream, (const __bf16*)x, ht, dw1, db1, M, H,
+                       B, sg);
   }
 }
 

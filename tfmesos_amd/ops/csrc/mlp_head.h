@@ -55,27 +55,48 @@ DEVINL void head_store_logits(float* ls, const f32x16v& acc, int row0,
 
 // rowwise softmax + dlogits over C <= 16 classes (scalar, one lane per
 // row): emit(c, d) receives d = (p - onehot) * scale per class;
-// returns -log p[label]
+// returns -log p[label] (0 for a label outside [0, C)). lr is a row of
+// the fp32 staging: all CP columns of it are written (zero logits
+// beyond C), so the row is read whole, up front — one LDS wait, not one
+// per class — and the loops are unrolled to CP behind c < C. The log is
+// taken once, of the selected p[label], after the class loop: the same
+// bits as a log inside it, at one transcendental per row instead of CP.
 template <class F>
 DEVINL float head_softmax_row(const float* lr, int C, int label,
                               float scale, F emit) {
-  float neglogp = 0.f;
+  float l[CP];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) l[c] = lr[c];
   float mx = -3.4e38f;
-  for (int c = 0; c < C; ++c) mx = fmaxf(mx, lr[c]);
+#pragma unroll
+  for (int c = 0; c < CP; ++c)
+    if (c < C) mx = fmaxf(mx, l[c]);
   float sum = 0.f;
-  float e[16];
-  for (int c = 0; c < C; ++c) {
-    e[c] = __expf(lr[c] - mx);
-    sum += e[c];
+  float e[CP];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    e[c] = 0.f;
+    if (c < C) {
+      e[c] = __expf(l[c] - mx);
+      sum += e[c];
+    }
   }
   const float inv = 1.f / sum;
-  for (int c = 0; c < C; ++c) {
-    const float p = e[c] * inv;
-    const float d = (p - (c == label ? 1.f : 0.f)) * scale;
-    emit(c, d);
-    if (c == label) neglogp = -__logf(fmaxf(p, 1e-30f));
+  float pl = 1.f;
+  bool hit = false;
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    if (c < C) {
+      const float p = e[c] * inv;
+      const float d = (p - (c == label ? 1.f : 0.f)) * scale;
+      emit(c, d);
+      if (c == label) {
+        pl = p;
+        hit = true;
+      }
+    }
   }
-  return neglogp;
+  return hit ? -__logf(fmaxf(pl, 1e-30f)) : 0.f;
 }
 
 // dh tile [32 rows, 32 hidden cols] = dls rows @ w^T, K = CP (one
