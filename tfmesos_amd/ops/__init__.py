@@ -23,6 +23,9 @@ and the key index of hashed embedding tables (TF's MutableHashTable):
 HashIndex, hash_find, hash_find_or_insert, hash_rebuild, hash_gather,
 hash_init_rows, hash_init_new_rows, and eviction from it: hash_touch (use
 stamps), hash_compact (keep the flagged rows, dense again), hash_remove.
+Feature admission: HashAdmission (a count-min sketch), hash_admit_cells,
+hash_find_or_admit, and the serving ops that read an absent key's initial
+row instead of storing it: hash_gather_init, hash_embedding_bag.
 """
 
 import collections
@@ -852,6 +855,126 @@ def hash_find_or_insert(index, keys):
     return torch.tensor(rows, dtype=torch.int64), is_new
 
 
+# Feature admission. Most keys of a hashed categorical feature are seen once
+# or twice and never again; a key earns a row only after it has been named
+# by ``admit_after`` push requests. The counts live in a count-min sketch:
+# 4 rows of ``width`` int32 counters, key k counts in cell
+# mix64(uint64(k) + (j + 1) * G) & (width - 1) of sketch row j (wrapping
+# uint64; mix64 and G as in hash_init_rows), its estimate is the minimum of
+# its four cells. Count-min never underestimates: a key is admitted no later
+# than its admit_after-th request, possibly earlier through collisions.
+
+HASH_ADMIT_ROWS = 4
+HASH_ADMIT_CAP = 2 ** 30    # counters saturate here
+
+
+def _admit_width_check(width):
+    if width < 64 or width & (width - 1):
+        raise ValueError("admission sketch: width must be a power of two "
+                         ">= 64, got %r" % (width,))
+
+
+def hash_admit_cells(keys, width):
+    """The sketch cells of every key: int64 [4, n] on the CPU, row j the
+    cells in sketch row j. Like ``hash_home`` an internal detail, exposed so
+    that a test can build collisions."""
+    _hash_keys_check(keys)
+    _admit_width_check(width)
+    k = _u64_array(keys)
+    cells = [_mix64(k + np.array([(j + 1) * _HASH_GOLD % _U64],
+                                 dtype=np.uint64)) & np.uint64(width - 1)
+             for j in range(HASH_ADMIT_ROWS)]
+    return torch.from_numpy(np.stack(cells).astype(np.int64))
+
+
+class HashAdmission(object):
+    """Count-min sketch of an admission policy: ``counters`` int32
+    [4, width] and ``filtered`` int64 [1] (distinct keys of a request that
+    were counted but not admitted, summed over the requests) on ``device``;
+    reading either is the caller's sync."""
+
+    def __init__(self, width, device="cpu"):
+        width = int(width)
+        _admit_width_check(width)
+        self.width = width
+        self.device = torch.device(device)
+        self.counters = torch.zeros(HASH_ADMIT_ROWS, width, dtype=torch.int32,
+                                    device=self.device)
+        self.filtered = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def decay(self):
+        """Halve every counter (ageing; plumbing, one torch op)."""
+        self.counters.bitwise_right_shift_(1)
+
+
+@torch.no_grad()
+def hash_find_or_admit(index, sketch, keys, admit_after):
+    """(rows int64 [n], is_new bool [n]): ``hash_find_or_insert`` behind the
+    admission sketch. A key that has a row behaves as there. Each DISTINCT
+    absent key of the request (HASH_EMPTY excluded) is counted once — its
+    four cells get +1, saturating: min(old + adds, 2**30) — whatever the
+    number of its occurrences, so coalescing a request does not change
+    which request admits a key. With all counts of the request in, an
+    absent key whose estimate (the minimum of its four cells) is >=
+    ``admit_after`` (in [1, 2**30]) is admitted: it is a new key of
+    ``hash_find_or_insert`` (rows in first-occurrence order among the
+    admitted keys, is_new at the first occurrence, -1 and ``dropped`` when
+    no room is left). Every other absent key gets -1 and
+    ``sketch.filtered`` grows by their number. Deterministic: the GPU
+    (csrc/hash.hip; integer atomics, decisions read in a later kernel)
+    equals this reference integer for integer, counters included."""
+    _hash_index_check(index, keys)
+    admit_after = int(admit_after)
+    if not 1 <= admit_after <= HASH_ADMIT_CAP:
+        raise ValueError("admit_after must lie in [1, 2**30], got %r"
+                         % (admit_after,))
+    if not isinstance(sketch, HashAdmission) or \
+            sketch.device != index.device:
+        raise ValueError("hash_find_or_admit: need a HashAdmission on the "
+                         "index's device")
+    if keys.is_cuda:
+        rows, is_new = _ext().hash_find_or_admit(
+            index.slot_keys, index.slot_rows, index.row_keys, index.size,
+            index.dropped, sketch.counters, sketch.filtered,
+            keys.contiguous(), admit_after)
+        return rows, is_new
+    m, cap = index._map, index.capacity
+    klist = keys.tolist()
+    first = {}                  # distinct absent keys -> first position
+    for i, k in enumerate(klist):
+        if k != HASH_EMPTY and k not in m and k not in first:
+            first[k] = i
+    is_new = torch.zeros(len(klist), dtype=torch.bool)
+    if first:
+        cand = torch.tensor(list(first), dtype=torch.int64)
+        cells = hash_admit_cells(cand, sketch.width).numpy()
+        counts = sketch.counters.numpy().astype(np.int64)
+        for j in range(HASH_ADMIT_ROWS):
+            np.add.at(counts[j], cells[j], 1)
+        np.minimum(counts, HASH_ADMIT_CAP, out=counts)
+        sketch.counters.copy_(torch.from_numpy(counts.astype(np.int32)))
+        est = np.stack([counts[j][cells[j]]
+                        for j in range(HASH_ADMIT_ROWS)]).min(axis=0)
+        admitted = est >= admit_after
+        sketch.filtered += int((~admitted).sum())
+        size, lost = int(index.size), 0
+        for k, ok in zip(first, admitted.tolist()):
+            if not ok:
+                continue
+            if size < cap:
+                m[k] = size
+                index.row_keys[size] = k
+                is_new[first[k]] = True
+                size += 1
+            else:
+                lost += 1
+        index.size.fill_(size)
+        index.dropped += lost
+    rows = torch.tensor([-1 if k == HASH_EMPTY else m.get(k, -1)
+                         for k in klist], dtype=torch.int64)
+    return rows, is_new
+
+
 @torch.no_grad()
 def hash_rebuild(index):
     """Rebuild the key -> row mapping from row_keys[0:size] (after
@@ -1024,6 +1147,112 @@ def hash_init_rows(keys, dim, seed, key_mul=1, key_add=0):
     z = _mix64(b[:, None] + cols[None, :])
     u = (z >> np.uint64(40)).astype(np.float32)
     return torch.from_numpy(u * np.float32(2.0 ** -24) * _hash_scale(dim))
+
+
+def _stamps_arg(op, last_used, keys):
+    if last_used is None:
+        return None
+    if last_used.dim() != 1 or last_used.dtype != torch.int64 or \
+            last_used.device != keys.device or not last_used.is_contiguous():
+        raise ValueError("%s: last_used must be a contiguous int64 "
+                         "[capacity] on the keys' device" % op)
+    return last_used
+
+
+def _absent_init_rows(rows, keys, dim, seed, key_mul, key_add):
+    """CPU: (which positions hold a real key without a row, the bf16
+    initial rows of those keys)."""
+    miss = (rows < 0) & (keys != HASH_EMPTY)
+    init = hash_init_rows(keys[miss], dim, seed, key_mul, key_add)
+    return miss, init.to(torch.bfloat16)
+
+
+@torch.no_grad()
+def hash_gather_init(index, table, keys, seed, key_mul=1, key_add=0,
+                     last_used=None, step=0):
+    """The training pull of a table with admission: ``hash_gather``, but a
+    key that has no row (HASH_EMPTY excepted, it still reads zeros) reads
+    bf16(its initial row) — ``hash_init_rows(keys, D, seed, key_mul,
+    key_add)``, the bits ``hash_init_new_rows`` would put into the shadow —
+    computed in registers, nothing stored. With ``last_used`` (int64
+    [capacity]) a hit stores ``step`` into last_used[row]. One launch on the
+    GPU. table bf16 [V,D]."""
+    _hash_index_check(index, keys)
+    if table.dim() != 2 or table.dtype != torch.bfloat16:
+        raise ValueError("hash_gather_init: table must be bf16 [V,D]")
+    last_used = _stamps_arg("hash_gather_init", last_used, keys)
+    if keys.is_cuda:
+        return _ext().hash_gather_init(
+            index.slot_keys, index.slot_rows, table, keys.contiguous(),
+            last_used if last_used is not None
+            else torch.empty(0, dtype=torch.int64, device=keys.device),
+            int(step), int(seed), int(key_mul), int(key_add),
+            float(_hash_scale(table.shape[1])))
+    rows = hash_find(index, keys)
+    out = _rows_or_zero(table, rows)
+    miss, init = _absent_init_rows(rows, keys, table.shape[1], seed, key_mul,
+                                   key_add)
+    out[miss] = init
+    if last_used is not None:
+        hash_touch(torch.where(rows < table.shape[0], rows,
+                               torch.full_like(rows, -1)), last_used, step)
+    return out
+
+
+@torch.no_grad()
+def hash_embedding_bag(index, table, keys, offsets, weights=None,
+                       combiner="sum", out_dtype=None, init=None,
+                       last_used=None, step=0):
+    """``embedding_bag`` by key, the lookup fused in (one launch on the
+    GPU): position i contributes c_i * table[row of keys[i]]. A key without
+    a row contributes nothing — but still counts in a mean's weight sum —
+    unless ``init=(seed, key_mul, key_add)`` is given: then it contributes
+    its initial row rounded to bf16 (``hash_init_rows``), computed in
+    registers. HASH_EMPTY never contributes. Bit for bit
+    ``embedding_bag(cat([table, bf16 initial rows of the absent keys]),
+    ids)`` with ids = the rows and the absent keys pointed at the appended
+    rows: same accumulation order, same arithmetic. With ``last_used`` the
+    rows of the keys inside the bags get ``step``. table bf16 [V,D], V >= 1;
+    out_dtype bf16 (default) or torch.float32."""
+    _hash_index_check(index, keys)
+    _bag_check(keys, offsets, weights, combiner)
+    if table.dim() != 2 or table.dtype != torch.bfloat16 or \
+            table.shape[0] < 1:
+        raise ValueError("hash_embedding_bag: table must be bf16 [V,D] with "
+                         "V >= 1")
+    out_dtype = table.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (table.dtype, torch.float32):
+        raise ValueError("hash_embedding_bag: out_dtype must be "
+                         "torch.bfloat16 or torch.float32")
+    last_used = _stamps_arg("hash_embedding_bag", last_used, keys)
+    seed, key_mul, key_add = (0, 1, 0) if init is None else init
+    if keys.is_cuda:
+        return _ext().hash_embedding_bag(
+            index.slot_keys, index.slot_rows, table, keys.contiguous(),
+            offsets.contiguous(), _bag_weights(weights, table.device),
+            combiner == "mean", out_dtype == torch.float32,
+            last_used if last_used is not None
+            else torch.empty(0, dtype=torch.int64, device=keys.device),
+            int(step), init is not None, int(seed), int(key_mul),
+            int(key_add), float(_hash_scale(table.shape[1])))
+    rows = hash_find(index, keys)
+    V = table.shape[0]
+    if init is not None:
+        miss, extra = _absent_init_rows(rows, keys, table.shape[1], seed,
+                                        key_mul, key_add)
+        ids = rows.clone()
+        ids[miss] = V + torch.arange(int(miss.sum()))
+        ids[rows >= V] = -1     # a row the table cannot hold: nothing
+        out = embedding_bag(torch.cat([table, extra]), ids, offsets,
+                            weights=weights, combiner=combiner,
+                            out_dtype=out_dtype)
+    else:
+        out = embedding_bag(table, rows, offsets, weights=weights,
+                            combiner=combiner, out_dtype=out_dtype)
+    if last_used is not None:
+        hash_touch(torch.where(rows < V, rows, torch.full_like(rows, -1)),
+                   last_used, step)
+    return out
 
 
 @torch.no_grad()

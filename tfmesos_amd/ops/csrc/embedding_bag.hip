@@ -5,7 +5,8 @@
 //   * one wave owns one (bag, 256-column tile): it reads the bag's ids
 //     (and weights) 64 positions at a time, one per lane, broadcasts each
 //     with a wave shuffle, keeps 4 row loads in flight and accumulates in
-//     fp32 registers in position order; the row is rounded once on store.
+//     fp32 registers in position order (bag_walk.h, shared with the keyed
+//     pooled pull of hash.hip); the row is rounded once on store.
 //     Fixed order, no atomics => bit-reproducible.
 //   * D % 4 == 0 and 16-byte aligned bases: lane l owns columns 4l..4l+3
 //     of the tile (bf16x4 / f32x4 accesses). Otherwise a scalar path:
@@ -19,12 +20,29 @@
 #include "common.h"
 #include "embedding_bag.h"
 
-#include "bag.h"
-#include "tile.h"
+#include "bag_walk.h"
 
 namespace {
 
 constexpr int WAVES = 4;    // waves per block
+
+// bag_walk's source over a table indexed by id: position p names row ids[p].
+template <typename T, int VEC>
+struct TableRows {
+  const T* __restrict__ table;
+  const long* __restrict__ ids;
+  long V;
+  int D, c0, lane;
+
+  DEVINL long item(long p, bool& valid) const {
+    const long id = ids[p];
+    valid = id >= 0 && id < V;
+    return id;
+  }
+  DEVINL void fetch(long id, int, float (&v)[ACC]) const {
+    ld_tile<T, VEC>(table + id * D, c0, lane, D, v);
+  }
+};
 
 template <typename T, typename O, int VEC>
 __global__ __launch_bounds__(WAVES * WAVE) void embedding_bag_kernel(
@@ -43,44 +61,8 @@ __global__ __launch_bounds__(WAVES * WAVE) void embedding_bag_kernel(
   float acc[ACC];
 #pragma unroll
   for (int k = 0; k < ACC; ++k) acc[k] = 0.f;
-  for (long p0 = s; p0 < e; p0 += WAVE) {
-    const long p = p0 + lane;
-    long id = p < e ? ids[p] : -1;
-    const bool valid = id >= 0 && id < V;
-    float cf = 0.f;
-    if (valid) cf = bag_coef(weights ? weights[p] : 1.f, W, mean != 0);
-    else id = 0;
-    // walk the valid lanes in position order, 4 row loads in flight
-    unsigned long long m = __ballot(valid);
-    while (__popcll(m) >= 4) {
-      const int k0 = __ffsll(m) - 1; m &= m - 1;
-      const int k1 = __ffsll(m) - 1; m &= m - 1;
-      const int k2 = __ffsll(m) - 1; m &= m - 1;
-      const int k3 = __ffsll(m) - 1; m &= m - 1;
-      const long r0 = __shfl(id, k0), r1 = __shfl(id, k1);
-      const long r2 = __shfl(id, k2), r3 = __shfl(id, k3);
-      const float f0 = __shfl(cf, k0), f1 = __shfl(cf, k1);
-      const float f2 = __shfl(cf, k2), f3 = __shfl(cf, k3);
-      float v0[ACC], v1[ACC], v2[ACC], v3[ACC];
-      ld_tile<T, VEC>(table + r0 * D, c0, lane, D, v0);
-      ld_tile<T, VEC>(table + r1 * D, c0, lane, D, v1);
-      ld_tile<T, VEC>(table + r2 * D, c0, lane, D, v2);
-      ld_tile<T, VEC>(table + r3 * D, c0, lane, D, v3);
-#pragma unroll
-      for (int k = 0; k < ACC; ++k)
-        acc[k] = (((acc[k] + f0 * v0[k]) + f1 * v1[k]) + f2 * v2[k]) +
-                 f3 * v3[k];
-    }
-    while (m) {
-      const int k0 = __ffsll(m) - 1; m &= m - 1;
-      const long r = __shfl(id, k0);
-      const float f = __shfl(cf, k0);
-      float v[ACC];
-      ld_tile<T, VEC>(table + r * D, c0, lane, D, v);
-#pragma unroll
-      for (int k = 0; k < ACC; ++k) acc[k] += f * v[k];
-    }
-  }
+  TableRows<T, VEC> src = {table, ids, V, D, c0, lane};
+  bag_walk(src, weights, s, e, W, mean != 0, lane, acc);
   st_tile<O, VEC>(out + b * D, c0, lane, D, acc);   // empty bag: zeros
 }
 

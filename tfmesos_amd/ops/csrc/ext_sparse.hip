@@ -425,12 +425,20 @@ torch::Tensor hash_find(torch::Tensor slot_keys, torch::Tensor slot_rows,
   return rows;
 }
 
-// rows [n] and is_new bool [n]; absent keys get the rows size, size + 1, ..
-// in order of first occurrence while they are below capacity (hash.hip).
-// The scratch fill and the scan of the flags are plumbing; no host sync.
-std::vector<torch::Tensor> hash_find_or_insert(
-    torch::Tensor slot_keys, torch::Tensor slot_rows, torch::Tensor row_keys,
-    torch::Tensor size, torch::Tensor dropped, torch::Tensor keys) {
+// An admission sketch in front of the insert: counters i32 [4, width] and
+// filtered i64 [1] on the keys' GPU.
+struct Admission {
+  torch::Tensor counters, filtered;
+  long admit_after;
+};
+
+// find_or_insert, behind a sketch when one is given (hash.hip). The scratch
+// fill and the scan of the flags are plumbing; no host sync.
+std::vector<torch::Tensor> find_or_insert(
+    const torch::Tensor& slot_keys, const torch::Tensor& slot_rows,
+    const torch::Tensor& row_keys, const torch::Tensor& size,
+    const torch::Tensor& dropped, const torch::Tensor& keys,
+    const Admission* admit) {
   const long H = hash_slots(slot_keys, slot_rows), n = hash_keys(keys);
   hash_counters(row_keys, size, H);
   TORCH_CHECK(i64_vec(dropped) && dropped.numel() == 1,
@@ -443,19 +451,64 @@ std::vector<torch::Tensor> hash_find_or_insert(
   while (S < 2 * n) S <<= 1;
   // [0] keys, [1] smallest position: both start at INT64_MIN
   auto scratch = torch::full({2, S}, (int64_t)LONG_MIN, opt);
-  auto flags = torch::empty({n}, opt.dtype(torch::kInt32));
+  // [0:n] first occurrences of absent keys, [n:2n] those of them that pass
+  auto flags = torch::empty({admit ? 2 * n : n}, opt.dtype(torch::kInt32));
   long* sk = scratch.data_ptr<long>();
+  int* fresh = flags.data_ptr<int>();
   launch_hash_lookup(keys.data_ptr<long>(), slot_keys.data_ptr<long>(),
                      slot_rows.data_ptr<long>(), rows.data_ptr<long>(), sk,
-                     sk + S, flags.data_ptr<int>(), n, H, S, cur_stream());
+                     sk + S, fresh, n, H, S, cur_stream());
+  if (admit) {
+    launch_hash_admit(keys.data_ptr<long>(), fresh,
+                      admit->counters.data_ptr<int>(), fresh + n,
+                      admit->filtered.data_ptr<long>(), n,
+                      admit->counters.size(1), admit->admit_after,
+                      cur_stream());
+    fresh += n;
+    flags = flags.narrow(0, n, n);
+  }
   auto incl = torch::cumsum(flags, 0, torch::kInt64);
-  launch_hash_insert(keys.data_ptr<long>(), flags.data_ptr<int>(),
-                     incl.data_ptr<long>(), slot_keys.data_ptr<long>(),
-                     slot_rows.data_ptr<long>(), row_keys.data_ptr<long>(),
-                     size.data_ptr<long>(), dropped.data_ptr<long>(),
-                     rows.data_ptr<long>(), is_new.data_ptr<bool>(), n, H,
-                     row_keys.numel(), cur_stream());
+  launch_hash_insert(keys.data_ptr<long>(), fresh, incl.data_ptr<long>(),
+                     slot_keys.data_ptr<long>(), slot_rows.data_ptr<long>(),
+                     row_keys.data_ptr<long>(), size.data_ptr<long>(),
+                     dropped.data_ptr<long>(), rows.data_ptr<long>(),
+                     is_new.data_ptr<bool>(), n, H, row_keys.numel(),
+                     cur_stream());
   return {rows, is_new};
+}
+
+// rows [n] and is_new bool [n]; absent keys get the rows size, size + 1, ..
+// in order of first occurrence while they are below capacity (hash.hip).
+std::vector<torch::Tensor> hash_find_or_insert(
+    torch::Tensor slot_keys, torch::Tensor slot_rows, torch::Tensor row_keys,
+    torch::Tensor size, torch::Tensor dropped, torch::Tensor keys) {
+  return find_or_insert(slot_keys, slot_rows, row_keys, size, dropped, keys,
+                        nullptr);
+}
+
+// find_or_insert behind a count-min admission sketch (hash.hip): an absent
+// key is counted once per request in counters int32 [4, width] and gets a
+// row only when its estimate has reached admit_after; the distinct keys
+// that did not are added to filtered.
+std::vector<torch::Tensor> hash_find_or_admit(
+    torch::Tensor slot_keys, torch::Tensor slot_rows, torch::Tensor row_keys,
+    torch::Tensor size, torch::Tensor dropped, torch::Tensor counters,
+    torch::Tensor filtered, torch::Tensor keys, long admit_after) {
+  TORCH_CHECK(i64_vec(filtered) && filtered.numel() == 1,
+              "hash_find_or_admit: filtered must be i64 [1] on GPU");
+  TORCH_CHECK(counters.is_cuda() && counters.scalar_type() == torch::kInt32 &&
+              counters.dim() == 2 && counters.size(0) == 4 &&
+              counters.is_contiguous() && counters.device() == keys.device(),
+              "hash_find_or_admit: counters must be contiguous i32 "
+              "[4, width] on the keys' GPU");
+  const long width = counters.size(1);
+  TORCH_CHECK(width >= 64 && (width & (width - 1)) == 0,
+              "hash_find_or_admit: width must be a power of two >= 64");
+  TORCH_CHECK(admit_after >= 1 && admit_after <= (1L << 30),
+              "hash_find_or_admit: admit_after must lie in [1, 2^30]");
+  const Admission admit = {counters, filtered, admit_after};
+  return find_or_insert(slot_keys, slot_rows, row_keys, size, dropped, keys,
+                        &admit);
 }
 
 // Clears the slot arrays and inserts row_keys[0:size] with their rows.
@@ -485,6 +538,80 @@ torch::Tensor hash_gather(torch::Tensor slot_keys, torch::Tensor slot_rows,
                      slot_rows.data_ptr<long>(),
                      (const bf16_t*)table.data_ptr(), (bf16_t*)out.data_ptr(),
                      n, H, V, (int)D, cur_stream());
+  return out;
+}
+
+// The use stamps of a serving kernel: null / 0 for an empty tensor.
+long* hash_stamps(const char* op, const torch::Tensor& last_used,
+                  const torch::Tensor& keys, long& count) {
+  count = last_used.numel();
+  if (count == 0) return nullptr;
+  TORCH_CHECK(i64_vec(last_used) && last_used.device() == keys.device(), op,
+              ": last_used must be contiguous i64 [capacity] on the keys' "
+              "GPU");
+  return last_used.data_ptr<long>();
+}
+
+// hash_gather with the key's initial row (bf16) on a miss; a hit stores step
+// into last_used[row] (numel 0: no stamps). One launch.
+torch::Tensor hash_gather_init(torch::Tensor slot_keys,
+                               torch::Tensor slot_rows, torch::Tensor table,
+                               torch::Tensor keys, torch::Tensor last_used,
+                               long step, long seed, long key_mul,
+                               long key_add, double scale) {
+  const long H = hash_slots(slot_keys, slot_rows), n = hash_keys(keys);
+  TORCH_CHECK(table.is_cuda() && table.dim() == 2 && table.is_contiguous() &&
+              table.scalar_type() == torch::kBFloat16,
+              "hash_gather_init: table must be contiguous bf16 [V,D] on GPU");
+  const long V = table.size(0), D = table.size(1);
+  TORCH_CHECK(D <= (long)INT_MAX, "hash_gather_init: D too large");
+  long stamps = 0;
+  long* lu = hash_stamps("hash_gather_init", last_used, keys, stamps);
+  auto out = torch::empty({n, D}, table.options());
+  if (n == 0 || D == 0) return out;
+  launch_hash_gather_init(keys.data_ptr<long>(), slot_keys.data_ptr<long>(),
+                          slot_rows.data_ptr<long>(),
+                          (const bf16_t*)table.data_ptr(),
+                          (bf16_t*)out.data_ptr(), lu, n, H, V, (int)D,
+                          stamps, step, seed, key_mul, key_add, (float)scale,
+                          cur_stream());
+  return out;
+}
+
+// Pooled pull by key (hash.hip): embedding_bag with the lookup fused in; with
+// has_init a key without a row contributes its bf16 initial row. out bf16,
+// or fp32 with out_f32.
+torch::Tensor hash_embedding_bag(torch::Tensor slot_keys,
+                                 torch::Tensor slot_rows, torch::Tensor table,
+                                 torch::Tensor keys, torch::Tensor offsets,
+                                 torch::Tensor weights, bool mean,
+                                 bool out_f32, torch::Tensor last_used,
+                                 long step, bool has_init, long seed,
+                                 long key_mul, long key_add, double scale) {
+  const long H = hash_slots(slot_keys, slot_rows);
+  TORCH_CHECK(table.is_cuda() && table.dim() == 2 && table.is_contiguous() &&
+              table.scalar_type() == torch::kBFloat16 && table.size(0) >= 1,
+              "hash_embedding_bag: table must be contiguous bf16 [V,D], "
+              "V >= 1, on GPU");
+  const float* w = bag_args("hash_embedding_bag", keys, offsets, weights);
+  const long n = hash_keys(keys), V = table.size(0);
+  const long B = offsets.numel() - 1, D = table.size(1);
+  TORCH_CHECK(D <= (long)INT_MAX, "hash_embedding_bag: D too large");
+  long stamps = 0;
+  long* lu = hash_stamps("hash_embedding_bag", last_used, keys, stamps);
+  auto out = torch::empty({B, D}, table.options().dtype(
+      out_f32 ? torch::kFloat32 : torch::kBFloat16));
+  if (B == 0 || D == 0) return out;   // a zero-size grid is a launch error
+  if (n == 0) return out.zero_();
+  TORCH_CHECK(B * ((D + 255) / 256) / 4 < (long)INT_MAX,
+              "hash_embedding_bag: B x D too large for one grid");
+  launch_hash_embedding_bag(keys.data_ptr<long>(), slot_keys.data_ptr<long>(),
+                            slot_rows.data_ptr<long>(),
+                            (const bf16_t*)table.data_ptr(),
+                            offsets.data_ptr<long>(), w, out.data_ptr(),
+                            !out_f32, lu, B, n, H, V, (int)D, mean, stamps,
+                            step, has_init, seed, key_mul, key_add,
+                            (float)scale, cur_stream());
   return out;
 }
 
@@ -666,6 +793,24 @@ void bind_sparse(pybind11::module_& m) {
         "rows of int64 keys, absent keys get the next free rows: rows, is_new",
         py::arg("slot_keys"), py::arg("slot_rows"), py::arg("row_keys"),
         py::arg("size"), py::arg("dropped"), py::arg("keys"));
+  m.def("hash_find_or_admit", &hash_find_or_admit,
+        "find_or_insert behind a count-min admission sketch: rows, is_new",
+        py::arg("slot_keys"), py::arg("slot_rows"), py::arg("row_keys"),
+        py::arg("size"), py::arg("dropped"), py::arg("counters"),
+        py::arg("filtered"), py::arg("keys"), py::arg("admit_after"));
+  m.def("hash_gather_init", &hash_gather_init,
+        "bf16 table rows of int64 keys, the initial row when absent",
+        py::arg("slot_keys"), py::arg("slot_rows"), py::arg("table"),
+        py::arg("keys"), py::arg("last_used"), py::arg("step"),
+        py::arg("seed"), py::arg("key_mul"), py::arg("key_add"),
+        py::arg("scale"));
+  m.def("hash_embedding_bag", &hash_embedding_bag,
+        "pooled pull by int64 key, optional initial rows for absent keys",
+        py::arg("slot_keys"), py::arg("slot_rows"), py::arg("table"),
+        py::arg("keys"), py::arg("offsets"), py::arg("weights"),
+        py::arg("mean"), py::arg("out_f32"), py::arg("last_used"),
+        py::arg("step"), py::arg("has_init"), py::arg("seed"),
+        py::arg("key_mul"), py::arg("key_add"), py::arg("scale"));
   m.def("hash_rebuild", &hash_rebuild,
         "clear the slots and insert row_keys[0:size]",
         py::arg("slot_keys"), py::arg("slot_rows"), py::arg("row_keys"),

@@ -25,6 +25,9 @@ void launch_hash_lookup(const long* keys, const long* slot_keys,
                         const long* slot_rows, long* rows, long* skeys,
                         long* spos, int* flags, long n, long H, long S,
                         hipStream_t stream);
+void launch_hash_admit(const long* keys, const int* flags, int* counters,
+                       int* pass, long* filtered, long n, long width,
+                       long admit_after, hipStream_t stream);
 void launch_hash_insert(const long* keys, const int* flags, const long* incl,
                         long* slot_keys, long* slot_rows, long* row_keys,
                         long* size, long* dropped, long* rows, bool* is_new,
@@ -41,3 +44,18 @@ void launch_hash_init_rows(const long* keys, const long* rows,
                            float* s1, float* s2, long n, long V, int D,
                            long seed, long key_mul, long key_add, float scale,
                            hipStream_t stream);
+void launch_hash_gather_init(const long* keys, const long* slot_keys,
+                             const long* slot_rows, const bf16_t* table,
+                             bf16_t* out, long* last_used, long n, long H,
+                             long V, int D, long stamps, long step, long seed,
+                             long key_mul, long key_add, float scale,
+                             hipStream_t stream);
+void launch_hash_embedding_bag(const long* keys, const long* slot_keys,
+                               const long* slot_rows, const bf16_t* table,
+                               const long* offsets, const float* weights,
+                               void* out, bool o_bf16, long* last_used,
+                               long B, long n, long H, long V, int D,
+                               bool mean, long stamps, long step,
+                               bool has_init, long seed, long key_mul,
+                               long key_add, float scale,
+                               hipStream_t stream);

@@ -47,6 +47,51 @@
 // copies the bf16 row (8 bytes per lane when D % 4 == 0 and the bases are
 // 8-byte aligned) or writes zeros on a miss: one launch per pull.
 //
+// find_or_admit(keys [n], sketch, admit_after) — feature admission: a key
+// earns a row only once it has been named by admit_after requests. The
+// sketch is count-min: counters int32 [4, width], width a power of two, the
+// cell of key k in sketch row j is mix64(k + (j + 1) * G) & (width - 1).
+// Kernels 1 and 2 above run unchanged (flag = first occurrence of an ABSENT
+// key: each distinct absent key of the request is counted once), then
+//   A. count: a flagged position adds 1 to its four cells (integer atomics).
+//   B. decide: a flagged position reads its four cells — all counts of the
+//      request are in, they were written by kernel A —, and pass[i] = the
+//      minimum >= admit_after; every wave adds its number of flagged
+//      positions that did not pass to `filtered` (one integer atomic per
+//      wave that has any).
+//   then the scan, insert and resolve run on the PASS flags: an admitted
+//   key is a new key of find_or_insert, every other absent key stays at -1.
+//   Saturation at CAP = 2^30: a count is atomicAdd(cell, 1), and an add that
+//   RETURNS a value >= CAP takes itself back (atomicSub). Why the final
+//   value is min(c0 + a, CAP) for a cell that starts at c0 <= CAP and gets a
+//   adds, in every interleaving: at any moment the cell holds c0 + kept +
+//   pending, kept = the adds that returned a value < CAP, pending = the adds
+//   that returned >= CAP and have not been taken back yet. An add is kept
+//   only when it saw less than CAP, so c0 + kept <= CAP throughout. The
+//   FIRST add that is not kept (in the order the memory system applies
+//   them) saw no pending ones, hence c0 + kept >= CAP at that moment, hence
+//   = CAP, and kept never shrinks. So either every add is kept (c0 + a <=
+//   CAP) or c0 + kept = CAP at the end; pending is 0 when the kernel ends.
+//   The cell is treated as unsigned: c0 + a < 2^30 + 2^31 does not wrap.
+//   Nothing reads a cell during kernel A; kernel B sees final values only.
+//   So rows, is_new, row_keys, size, dropped, filtered and every counter are
+//   the same from run to run.
+//
+// hash_gather_init (training pull of a table with admission): hash_gather,
+// but a miss on a key other than EMPTY writes the bf16 of the key's INITIAL
+// row, computed in registers (the bits init_rows_kernel would have put into
+// the shadow); with last_used given, lane 0 stores step into last_used[row]
+// on a hit (a plain store, as in touch_kernel). One launch.
+//
+// hash_embedding_bag (pooled pull by key): embedding_bag.hip's kernel with
+// the lookup fused in. Each lane probes the key of its own position, then
+// the wave walks the rows exactly as embedding_bag_kernel does (bag_walk.h:
+// one walk, two row sources). With an initialiser given, a key that has no
+// row contributes bf2f(f2bf(initial value)), computed in registers; without
+// one it contributes nothing but still counts in a mean's weight sum. EMPTY
+// never contributes. Bit for bit embedding_bag over the table extended by
+// the bf16 initial rows of the absent keys.
+//
 // Row initialiser: value(seed, k, c) =
 //     float(mix64(mix64(mix64(seed + G) ^ k) + c * G) >> 40) * 2^-24 * scale
 // with G = 0x9E3779B97F4A7C15, mix64 the splitmix64 finaliser, k =
@@ -92,7 +137,7 @@
 
 #include <climits>
 
-#include "tile.h"
+#include "bag_walk.h"
 
 namespace {
 
@@ -100,6 +145,8 @@ constexpr int BLOCK = 256;
 constexpr int WAVES = 4;   // waves per block of the wave-per-item kernels
 constexpr long EMPTY = LONG_MIN;
 constexpr unsigned long long GOLD = 0x9E3779B97F4A7C15ull;
+constexpr int SKETCH_ROWS = 4;
+constexpr unsigned SKETCH_CAP = 1u << 30;   // counters saturate here
 
 typedef unsigned long long u64;
 
@@ -186,6 +233,52 @@ __global__ __launch_bounds__(BLOCK) void flag_kernel(
   flags[i] = flag;
 }
 
+// The cell of key in sketch row j; width: a power of two
+DEVINL long sketch_cell(long key, int j, long width) {
+  return (long)(mix64((u64)key + (u64)(j + 1) * GOLD) & (u64)(width - 1));
+}
+
+// find_or_admit A: every flagged position (the first occurrence of an absent
+// key) counts once in its four cells; saturating (file header).
+__global__ __launch_bounds__(BLOCK) void count_kernel(
+    const long* __restrict__ keys, const int* __restrict__ flags,
+    unsigned* __restrict__ counters, long n, long width) {
+  const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n || !flags[i]) return;
+  const long key = keys[i];
+#pragma unroll
+  for (int j = 0; j < SKETCH_ROWS; ++j) {
+    unsigned* cell = counters + j * width + sketch_cell(key, j, width);
+    if (atomicAdd(cell, 1u) >= SKETCH_CAP) atomicSub(cell, 1u);
+  }
+}
+
+// find_or_admit B: pass[i] = flagged and min of the four cells >=
+// admit_after; the flagged positions that do not pass are counted in
+// filtered, one atomic per wave that has any.
+__global__ __launch_bounds__(BLOCK) void decide_kernel(
+    const long* __restrict__ keys, const int* __restrict__ flags,
+    const unsigned* __restrict__ counters, int* __restrict__ pass,
+    long* __restrict__ filtered, long n, long width, unsigned admit_after) {
+  const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+  const bool flagged = i < n && flags[i];
+  bool ok = false;
+  if (flagged) {
+    const long key = keys[i];
+    unsigned est = counters[sketch_cell(key, 0, width)];
+#pragma unroll
+    for (int j = 1; j < SKETCH_ROWS; ++j) {
+      const unsigned c = counters[j * width + sketch_cell(key, j, width)];
+      est = c < est ? c : est;
+    }
+    ok = est >= admit_after;
+  }
+  if (i < n) pass[i] = ok;
+  const unsigned long long out = __ballot(flagged && !ok);
+  if (out && (threadIdx.x & (WAVE - 1)) == 0)
+    atomicAdd((u64*)filtered, (u64)__popcll(out));
+}
+
 // find_or_insert 3: publish the new keys that have room.
 __global__ __launch_bounds__(BLOCK) void insert_kernel(
     const long* __restrict__ keys, const int* __restrict__ flags,
@@ -242,15 +335,11 @@ __global__ __launch_bounds__(BLOCK) void rebuild_kernel(
   if (s >= 0) slot_rows[s] = r;
 }
 
-template <int VEC>
-__global__ __launch_bounds__(WAVES * WAVE) void hash_gather_kernel(
-    const long* __restrict__ keys, const long* __restrict__ slot_keys,
-    const long* __restrict__ slot_rows, const bf16_t* __restrict__ table,
-    bf16_t* __restrict__ out, long n, long H, long V, int D) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const long w = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
-  if (w >= n) return;   // wave-uniform
-  const long key = keys[w];
+// The row of key (the same in all 64 lanes), -1 when absent or EMPTY: the
+// wave reads 64 consecutive slots per step, one per lane.
+DEVINL long wave_find(const long* __restrict__ slot_keys,
+                      const long* __restrict__ slot_rows, long key, long H,
+                      int lane) {
   long row = -1;
   if (key != EMPTY) {
     const long base = home_slot(key, H);
@@ -267,6 +356,18 @@ __global__ __launch_bounds__(WAVES * WAVE) void hash_gather_kernel(
       if (gap) break;
     }
   }
+  return row;
+}
+
+template <int VEC>
+__global__ __launch_bounds__(WAVES * WAVE) void hash_gather_kernel(
+    const long* __restrict__ keys, const long* __restrict__ slot_keys,
+    const long* __restrict__ slot_rows, const bf16_t* __restrict__ table,
+    bf16_t* __restrict__ out, long n, long H, long V, int D) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const long w = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (w >= n) return;   // wave-uniform
+  const long row = wave_find(slot_keys, slot_rows, keys[w], H, lane);
   const bool live = row >= 0 && row < V;
   const bf16_t* src = table + (live ? row : 0) * D;
   bf16_t* dst = out + w * D;
@@ -285,6 +386,131 @@ __global__ __launch_bounds__(WAVES * WAVE) void hash_gather_kernel(
 DEVINL float init_value(u64 b, int col, float scale) {
   const u64 z = mix64(b + (u64)col * GOLD);
   return (float)(unsigned)(z >> 40) * 0x1p-24f * scale;
+}
+
+// What the initialiser needs besides the key and the column.
+struct InitArgs {
+  long seed, key_mul, key_add;
+  float scale;
+};
+
+// The per-key base of init_value: mix64(mix64(seed + G) ^ global key).
+DEVINL u64 init_base(const InitArgs& a, long key) {
+  const u64 k = (u64)key * (u64)a.key_mul + (u64)a.key_add;
+  return mix64(mix64((u64)a.seed + GOLD) ^ k);
+}
+
+// The lane's ACC elements (tile.h layout) of the initial row of a key, as
+// the bf16 shadow holds them; columns at or beyond D are 0.
+template <int VEC>
+DEVINL void init_tile(u64 b, float scale, int c0, int lane, int D,
+                      float (&v)[ACC]) {
+#pragma unroll
+  for (int e = 0; e < ACC; ++e) {
+    const int col = VEC == 4 ? c0 + lane * 4 + e : c0 + e * WAVE + lane;
+    v[e] = col < D ? bf2f(f2bf(init_value(b, col, scale))) : 0.f;
+  }
+}
+
+// hash_gather with the initial row on a miss; stamps hits. One wave per key.
+// last_used may be null; stamps = its length.
+template <int VEC>
+__global__ __launch_bounds__(WAVES * WAVE) void hash_gather_init_kernel(
+    const long* __restrict__ keys, const long* __restrict__ slot_keys,
+    const long* __restrict__ slot_rows, const bf16_t* __restrict__ table,
+    bf16_t* __restrict__ out, long* __restrict__ last_used, long n, long H,
+    long V, int D, long stamps, long step, InitArgs init) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const long w = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (w >= n) return;   // wave-uniform
+  const long key = keys[w];
+  const long row = wave_find(slot_keys, slot_rows, key, H, lane);
+  const bool live = row >= 0 && row < V;
+  bf16_t* dst = out + w * D;
+  if (live) {
+    if (last_used && lane == 0 && row < stamps) last_used[row] = step;
+    const bf16_t* src = table + row * D;
+    if constexpr (VEC == 4) {
+      for (int c = lane * 4; c < D; c += WAVE * 4)
+        *(bf16x4*)(__bf16*)(dst + c) = *(const bf16x4*)(const __bf16*)(src + c);
+    } else {
+      for (int c = lane; c < D; c += WAVE) dst[c] = src[c];
+    }
+    return;
+  }
+  // a row the table cannot hold (row >= V) reads as zeros, like EMPTY
+  const bool fresh = row < 0 && key != EMPTY;
+  const u64 b = fresh ? init_base(init, key) : 0;
+  for (int c0 = 0; c0 < D; c0 += TILE) {
+    float v[ACC];
+#pragma unroll
+    for (int e = 0; e < ACC; ++e) v[e] = 0.f;
+    if (fresh) init_tile<VEC>(b, init.scale, c0, lane, D, v);
+    st_tile<bf16_t, VEC>(dst, c0, lane, D, v);
+  }
+}
+
+// bag_walk's source over a table indexed by KEY: position p names the row
+// of keys[p]; a key without a row names its initial row when has_init.
+template <int VEC>
+struct KeyedRows {
+  const long* __restrict__ keys;
+  const long* __restrict__ slot_keys;
+  const long* __restrict__ slot_rows;
+  const bf16_t* __restrict__ table;
+  long* __restrict__ last_used;   // stamped by the wave of tile 0; or null
+  long H, V, stamps, step;
+  int D, c0, lane;
+  bool has_init;
+  InitArgs init;
+  long key;                       // the lane's own
+
+  DEVINL long item(long p, bool& valid) {
+    key = keys[p];
+    const long r = probe_find(slot_keys, slot_rows, key, H);
+    if (r >= 0) {
+      valid = r < V;
+      if (last_used && c0 == 0 && r < stamps) last_used[r] = step;
+      return r;
+    }
+    valid = has_init && key != EMPTY;
+    return -1;
+  }
+  // the load is issued before the (wave-uniform) branch, so that four of
+  // them stay in flight when every key has a row; V >= 1
+  DEVINL void fetch(long r, int k, float (&v)[ACC]) {
+    ld_tile<bf16_t, VEC>(table + (r > 0 ? r : 0) * D, c0, lane, D, v);
+    if (r < 0)
+      init_tile<VEC>(init_base(init, __shfl(key, k)), init.scale, c0, lane, D,
+                     v);
+  }
+};
+
+// One wave per (bag, 256-column tile), as embedding_bag_kernel.
+template <typename O, int VEC>
+__global__ __launch_bounds__(WAVES * WAVE) void hash_bag_kernel(
+    const long* __restrict__ keys, const long* __restrict__ slot_keys,
+    const long* __restrict__ slot_rows, const bf16_t* __restrict__ table,
+    const long* __restrict__ offsets, const float* __restrict__ weights,
+    O* __restrict__ out, long* __restrict__ last_used, long B, long n, long H,
+    long V, int D, int tiles, int mean, long stamps, long step, int has_init,
+    InitArgs init) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const long w = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (w >= B * tiles) return;   // wave-uniform
+  const long b = w / tiles;
+  const int c0 = (int)(w % tiles) * TILE;
+  long s, e;
+  bag_range(offsets, b, n, s, e);
+  const float W = mean ? bag_weight_sum(weights, s, e, lane) : 0.f;
+  float acc[ACC];
+#pragma unroll
+  for (int k = 0; k < ACC; ++k) acc[k] = 0.f;
+  KeyedRows<VEC> src = {keys, slot_keys, slot_rows, table, last_used, H, V,
+                        stamps, step, D, c0, lane, has_init != 0, init,
+                        EMPTY};
+  bag_walk(src, weights, s, e, W, mean != 0, lane, acc);
+  st_tile<O, VEC>(out + b * D, c0, lane, D, acc);   // empty bag: zeros
 }
 
 // One wave per (position, 256-column tile); s1 / s2 may be null.
@@ -514,6 +740,19 @@ void launch_hash_insert(const long* keys, const int* flags, const long* incl,
                      H, capacity);
 }
 
+// Kernels A and B of find_or_admit, between launch_hash_lookup and the scan:
+// counters int32 [4, width], width a power of two; flags / pass int32 [n];
+// filtered int64 [1]; 1 <= admit_after <= 2^30; n > 0.
+void launch_hash_admit(const long* keys, const int* flags, int* counters,
+                       int* pass, long* filtered, long n, long width,
+                       long admit_after, hipStream_t stream) {
+  hipLaunchKernelGGL(count_kernel, lanes_grid(n), dim3(BLOCK), 0, stream,
+                     keys, flags, (unsigned*)counters, n, width);
+  hipLaunchKernelGGL(decide_kernel, lanes_grid(n), dim3(BLOCK), 0, stream,
+                     keys, flags, (const unsigned*)counters, pass, filtered,
+                     n, width, (unsigned)admit_after);
+}
+
 // slot_keys filled with INT64_MIN by the caller; capacity > 0.
 void launch_hash_rebuild(const long* row_keys, const long* size,
                          long* slot_keys, long* slot_rows, long H,
@@ -556,4 +795,73 @@ void launch_hash_init_rows(const long* keys, const long* rows,
     hipLaunchKernelGGL(init_rows_kernel<1>, grid, dim3(WAVES * WAVE), 0,
                        stream, keys, rows, is_new, master, shadow, s1, s2, n,
                        V, D, tiles, seed, key_mul, key_add, scale);
+}
+
+// table bf16 [V,D] -> out bf16 [n,D], a miss reads the key's initial row;
+// last_used int64 [stamps] or null; n, D > 0.
+void launch_hash_gather_init(const long* keys, const long* slot_keys,
+                             const long* slot_rows, const bf16_t* table,
+                             bf16_t* out, long* last_used, long n, long H,
+                             long V, int D, long stamps, long step, long seed,
+                             long key_mul, long key_add, float scale,
+                             hipStream_t stream) {
+  const dim3 grid((unsigned)((n + WAVES - 1) / WAVES));
+  const InitArgs init = {seed, key_mul, key_add, scale};
+  const uintptr_t bases = (uintptr_t)table | (uintptr_t)out;
+  if ((D % 4) == 0 && (bases % 8) == 0)
+    hipLaunchKernelGGL(hash_gather_init_kernel<4>, grid, dim3(WAVES * WAVE),
+                       0, stream, keys, slot_keys, slot_rows, table, out,
+                       last_used, n, H, V, D, stamps, step, init);
+  else
+    hipLaunchKernelGGL(hash_gather_init_kernel<1>, grid, dim3(WAVES * WAVE),
+                       0, stream, keys, slot_keys, slot_rows, table, out,
+                       last_used, n, H, V, D, stamps, step, init);
+}
+
+namespace {
+
+template <typename O>
+void launch_bag_typed(const long* keys, const long* slot_keys,
+                      const long* slot_rows, const bf16_t* table,
+                      const long* offsets, const float* weights, O* out,
+                      long* last_used, long B, long n, long H, long V, int D,
+                      bool mean, long stamps, long step, bool has_init,
+                      const InitArgs& init, hipStream_t stream) {
+  const int tiles = (D + TILE - 1) / TILE;
+  const dim3 block(WAVES * WAVE);
+  const dim3 grid((unsigned)((B * tiles + WAVES - 1) / WAVES));
+  if (tile_vec4(D, table, out))
+    hipLaunchKernelGGL((hash_bag_kernel<O, 4>), grid, block, 0, stream, keys,
+                       slot_keys, slot_rows, table, offsets, weights, out,
+                       last_used, B, n, H, V, D, tiles, (int)mean, stamps,
+                       step, (int)has_init, init);
+  else
+    hipLaunchKernelGGL((hash_bag_kernel<O, 1>), grid, block, 0, stream, keys,
+                       slot_keys, slot_rows, table, offsets, weights, out,
+                       last_used, B, n, H, V, D, tiles, (int)mean, stamps,
+                       step, (int)has_init, init);
+}
+
+}  // namespace
+
+// table bf16 [V,D], V >= 1; out [B,D] bf16 or fp32; weights may be null;
+// last_used int64 [stamps] or null; B, n, D > 0.
+void launch_hash_embedding_bag(const long* keys, const long* slot_keys,
+                               const long* slot_rows, const bf16_t* table,
+                               const long* offsets, const float* weights,
+                               void* out, bool o_bf16, long* last_used,
+                               long B, long n, long H, long V, int D,
+                               bool mean, long stamps, long step,
+                               bool has_init, long seed, long key_mul,
+                               long key_add, float scale,
+                               hipStream_t stream) {
+  const InitArgs init = {seed, key_mul, key_add, scale};
+  if (o_bf16)
+    launch_bag_typed(keys, slot_keys, slot_rows, table, offsets, weights,
+                     (bf16_t*)out, last_used, B, n, H, V, D, mean, stamps,
+                     step, has_init, init, stream);
+  else
+    launch_bag_typed(keys, slot_keys, slot_rows, table, offsets, weights,
+                     (float*)out, last_used, B, n, H, V, D, mean, stamps,
+                     step, has_init, init, stream);
 }

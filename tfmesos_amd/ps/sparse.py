@@ -537,6 +537,31 @@ class HashedEmbeddingTable(_SparseOptimizer):
       ever served looks idle; every other request stamps the rows it names.
       Without tracking nothing is allocated and no request launches
       anything more than before.
+    * Admission (``admit_after=k``, off by default): a key earns a row only
+      once ``k`` PUSH requests have named it (``ops.hash_find_or_admit``; a
+      request counts a key once, whatever its occurrences, so worker-side
+      coalescing changes nothing). The counts live in a count-min sketch of
+      ``admit_width`` counters per row (default ``ops.hash_slots(capacity)``;
+      ``reserve`` leaves it alone), which never underestimates: the ``k``-th
+      push admits the key at the latest — it initialises the row and that
+      push's gradient applies —, a collision may admit it earlier. The
+      gradient of an unadmitted key is dropped and ``stats()["filtered"]``
+      counts it, once per request. Pulls never insert and never count,
+      whatever ``insert_on_pull`` says: with ``insert_on_pull=True`` a key
+      without a row is SERVED its exact initial row, computed on the fly and
+      not stored (one launch: ``ops.hash_gather_init`` /
+      ``ops.hash_embedding_bag``), so the model sees what it would have seen
+      without admission until the key's first applied gradient; this holds
+      for a key a full table has no room for, too. With
+      ``insert_on_pull=False`` unknown keys read zeros as before.
+      ``admit_decay_every=E`` halves the counters after every push that
+      leaves ``step % E == 0`` (no host sync). An evicted key that returns
+      is a first-seen key and must be admitted AGAIN — but its counters are
+      not cleared at the eviction (a count-min sketch cannot delete), so
+      without decay it is readmitted by its next push. Every ``shard_of``
+      shard owns a sketch over its local keys. Without ``admit_after``
+      nothing is allocated and no request launches anything more than
+      before.
     * Sharding: ``shard_of`` shards take keys in ``[0,
       ops.HASH_KEY_SPACE)`` = [0, 2**62) and the "mod" strategy only
       (``SparseWorkerClient(table_homes={name: [ranks]}, rows={name:
@@ -547,11 +572,24 @@ class HashedEmbeddingTable(_SparseOptimizer):
     def __init__(self, name, dim, capacity, device="cpu", lr=0.01, seed=0,
                  optimizer="sgd", insert_on_pull=True, key_mul=1, key_add=0,
                  track_use=False, max_idle=None, evict_every=None,
+                 admit_after=None, admit_width=None, admit_decay_every=None,
                  **hparams):
         """key_mul / key_add (``shard_of`` sets them): local key k stands
         for the global key k * key_mul + key_add in the initialiser.
         track_use / max_idle / evict_every: use stamps and the automatic
-        eviction policy (class docstring)."""
+        eviction policy; admit_after / admit_width / admit_decay_every:
+        feature admission (class docstring)."""
+        if admit_after is None and (admit_width is not None or
+                                    admit_decay_every is not None):
+            raise ValueError("admit_width and admit_decay_every need "
+                             "admit_after")
+        if admit_after is not None and not \
+                1 <= int(admit_after) <= ops.HASH_ADMIT_CAP:
+            raise ValueError("admit_after must lie in [1, 2**30], got %r"
+                             % (admit_after,))
+        if admit_decay_every is not None and int(admit_decay_every) < 1:
+            raise ValueError("admit_decay_every must be >= 1, got %r"
+                             % (admit_decay_every,))
         if (max_idle is None) != (evict_every is None):
             raise ValueError("max_idle and evict_every go together, got "
                              "max_idle=%r, evict_every=%r"
@@ -578,6 +616,14 @@ class HashedEmbeddingTable(_SparseOptimizer):
         self.last_used = torch.zeros(
             self.index.capacity, dtype=torch.int64,
             device=self.device) if self.track_use else None
+        self.admit_after = None if admit_after is None else int(admit_after)
+        self.admit_decay_every = None if admit_decay_every is None \
+            else int(admit_decay_every)
+        self.sketch = None
+        if self.admit_after is not None:
+            self.sketch = ops.HashAdmission(
+                ops.hash_slots(self.index.capacity) if admit_width is None
+                else admit_width, self.device)
         self.lock = threading.Lock()
 
     @property
@@ -610,7 +656,9 @@ class HashedEmbeddingTable(_SparseOptimizer):
         [0, ops.HASH_KEY_SPACE). ``track_use`` / ``max_idle`` /
         ``evict_every`` pass through: every shard stamps and evicts by its
         OWN ``step``, which moves in lockstep with the other shards' as
-        long as every push reaches every shard (the stock client's do)."""
+        long as every push reaches every shard (the stock client's do).
+        ``admit_after`` / ``admit_width`` / ``admit_decay_every`` pass
+        through as well: every shard owns a sketch over its local keys."""
         if not 1 <= num_shards <= 64 or not 0 <= shard < num_shards:
             raise ValueError("need 1 <= num_shards <= 64 and 0 <= shard < "
                              "num_shards, got shard %r of %r"
@@ -620,12 +668,17 @@ class HashedEmbeddingTable(_SparseOptimizer):
 
     def _rows(self, keys, insert):
         """Key -> row translation of one request (lock held): with
-        ``insert`` absent keys get rows, initialised in the same breath."""
+        ``insert`` absent keys get rows (the admitted ones, on a table with
+        admission), initialised in the same breath."""
         keys = keys.to(self.device)
         if not insert:
             rows = ops.hash_find(self.index, keys)
         else:
-            rows, is_new = ops.hash_find_or_insert(self.index, keys)
+            if self.sketch is None:
+                rows, is_new = ops.hash_find_or_insert(self.index, keys)
+            else:
+                rows, is_new = ops.hash_find_or_admit(
+                    self.index, self.sketch, keys, self.admit_after)
             ops.hash_init_new_rows(keys, rows, is_new, self.master,
                                    self.shadow, list(self.state.values()),
                                    self.seed, self.key_mul, self.key_add)
@@ -638,9 +691,15 @@ class HashedEmbeddingTable(_SparseOptimizer):
         return [self.master, self.shadow] + list(self.state.values())
 
     def _auto_evict(self):
-        """The automatic policy, after a push's apply (lock held)."""
+        """The automatic policies, after a push's apply (lock held)."""
         if self.evict_every and self.step % self.evict_every == 0:
             self._evict(self.max_idle, None)
+        if self.admit_decay_every and \
+                self.step % self.admit_decay_every == 0:
+            self.sketch.decay()
+
+    def _init_args(self):
+        return (self.seed, self.key_mul, self.key_add)
 
     def _evict(self, max_idle, target_size):
         """One compaction for both rules (lock held)."""
@@ -694,11 +753,17 @@ class HashedEmbeddingTable(_SparseOptimizer):
             self._evict(max_idle, target_size)
 
     def pull(self, ids):
-        """bf16 rows for the keys ``ids``; zero rows for keys without one."""
+        """bf16 rows for the keys ``ids``; zero rows for keys without one
+        (with admission and ``insert_on_pull``: their initial rows)."""
         with self.lock:
             if not self.insert_on_pull:
                 return ops.hash_gather(self.index, self.shadow,
                                        ids.to(self.device))
+            if self.sketch is not None:
+                return ops.hash_gather_init(
+                    self.index, self.shadow, ids.to(self.device),
+                    *self._init_args(), last_used=self.last_used,
+                    step=self.step)
             rows = self._rows(ids, True)
             if self.device.type == "cpu":   # index_select cannot take -1
                 return ops._rows_or_zero(self.shadow, rows)
@@ -715,8 +780,15 @@ class HashedEmbeddingTable(_SparseOptimizer):
     def pull_pooled(self, ids, offsets, weights=None, combiner="sum",
                     out_dtype=None):
         """``EmbeddingTable.pull_pooled`` over keys; a key without a row
-        contributes nothing but still counts in a mean's weight sum."""
+        contributes nothing but still counts in a mean's weight sum (with
+        admission and ``insert_on_pull`` it contributes its initial row)."""
         with self.lock:
+            if self.sketch is not None and self.insert_on_pull:
+                return ops.hash_embedding_bag(
+                    self.index, self.shadow, ids.to(self.device), offsets,
+                    weights=weights, combiner=combiner, out_dtype=out_dtype,
+                    init=self._init_args(), last_used=self.last_used,
+                    step=self.step)
             rows = self._rows(ids, self.insert_on_pull)
             return ops.embedding_bag(self.shadow, rows, offsets,
                                      weights=weights, combiner=combiner,
@@ -737,16 +809,21 @@ class HashedEmbeddingTable(_SparseOptimizer):
         """{"size", "dropped", "capacity"}, and "evicted" (rows removed by
         ``evict`` / ``remove`` so far) on a table that tracks use — THE
         place that syncs: the counters live on the device and nothing else
-        reads them."""
+        reads them. A table with admission adds "filtered": the keys that
+        were counted but not admitted, once per request and distinct key."""
         with self.lock:
             counters = [self.index.size, self.index.dropped]
             if self.track_use:
                 counters.append(self.index.evicted)
-            size, dropped, *evicted = torch.cat(counters).tolist()
+            if self.sketch is not None:
+                counters.append(self.sketch.filtered)
+            size, dropped, *more = torch.cat(counters).tolist()
             out = {"size": size, "dropped": dropped,
                    "capacity": self.index.capacity}
             if self.track_use:
-                out["evicted"] = evicted[0]
+                out["evicted"] = more.pop(0)
+            if self.sketch is not None:
+                out["filtered"] = more.pop(0)
             return out
 
     def reserve(self, capacity):
@@ -774,7 +851,8 @@ class HashedEmbeddingTable(_SparseOptimizer):
         """keys = row_keys[:size], the first ``size`` rows of master and
         optimizer state, step and seed (CPU copies); row r belongs to
         keys[r]. A table that tracks use adds "last_used", the first
-        ``size`` stamps."""
+        ``size`` stamps; a table with admission adds "admit_counters", the
+        whole sketch."""
         with self.lock:
             n = int(self.index.size)
             sd = {
@@ -788,15 +866,27 @@ class HashedEmbeddingTable(_SparseOptimizer):
             }
             if self.track_use:
                 sd["last_used"] = self.last_used[:n].cpu().clone()
+            if self.sketch is not None:
+                sd["admit_counters"] = self.sketch.counters.cpu().clone()
             return sd
 
     def load_state_dict(self, sd):
         """Load into this table (any capacity >= the checkpoint's size):
         the keys keep their rows, index and shadow are rebuilt, and the
         table takes the checkpoint's seed — it then trains on exactly as
-        the saved one would have."""
+        the saved one would have. The admission sketch is restored from
+        "admit_counters" (same width); a checkpoint without it loads with a
+        zero sketch."""
         self._check_state_dict(sd)
         n = sd["keys"].numel()
+        counters = sd.get("admit_counters") if self.sketch is not None \
+            else None
+        if counters is not None and \
+                counters.shape != self.sketch.counters.shape:
+            raise ValueError("checkpoint sketch is %s, table %r has %s "
+                             "(admit_width)"
+                             % (tuple(counters.shape), self.name,
+                                tuple(self.sketch.counters.shape)))
         if n > self.index.capacity:
             raise ValueError("checkpoint holds %d keys, table %r has "
                              "capacity %d" % (n, self.name,
@@ -814,6 +904,12 @@ class HashedEmbeddingTable(_SparseOptimizer):
                     self.last_used[:n].copy_(sd["last_used"])
                 else:
                     self.last_used[:n].fill_(self.step)
+            if self.sketch is not None:
+                self.sketch.filtered.zero_()
+                if counters is not None:
+                    self.sketch.counters.copy_(counters)
+                else:
+                    self.sketch.counters.zero_()
 
 
 def make_sparse_pair_groups(ps_ranks, worker_ranks):
