@@ -298,15 +298,19 @@ void conv_reduce_kernel(const float* __restrict__ ws,
   float* Yf = (float*)Yv;
   const long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i0 >= mk) return;
+  // slice s starts at ws + s*mk: 16 B aligned for every s only when
+  // mk % 4 == 0 (then i0 + 4 <= mk holds for every live thread too);
+  // uniform per launch
+  const bool v4 = (mk & 3) == 0;
   f32x4 v = {};
   for (int s = 0; s < z; ++s) {
     const float* p = ws + (long)s * mk + i0;
-    if (i0 + 4 <= mk) {
+    if (v4) {
       const f32x4 sv = *(const f32x4*)p;
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] += sv[j];
     } else {
-      for (int j = 0; i0 + j < mk; ++j) v[j] += p[j];
+      for (int j = 0; j < 4 && i0 + j < mk; ++j) v[j] += p[j];
     }
   }
 #pragma unroll
@@ -509,7 +513,10 @@ void conv_bwdd_kernel(const __bf16* __restrict__ dY, const __bf16* __restrict__ 
   __shared__ __align__(16) __bf16 Bs[2][TRB ? TR_ELEMS : TILE_ELEMS];
   const long M = (long)cs.N * cs.H * cs.W;
   const int KD = cs.R * cs.S * cs.K;
-  const bool kvec = (cs.K & 7) == 0;
+  // b128 dY loads need the 8-k chunk 16 B aligned: base + p*LDY + kc0
+  // (dY may be a channel-narrow view at any offset / row stride)
+  const bool kvec = ((cs.K & 7) == 0) && ((cs.LDY & 7) == 0) &&
+                    ((((unsigned long long)dY) & 15ULL) == 0);
   const long tm0 = (long)blockIdx.x * BM;
   const int tn0 = blockIdx.y * BN;
   const int t = threadIdx.x;
@@ -605,7 +612,7 @@ struct DyBwdwStage {
   int k, pxc;
   bool kok;
   long p;              // first pixel of this thread's chunk
-  const __bf16* src;   // advances by BK*K per tile
+  const __bf16* src;   // advances by BK*LDY per tile
   bf16x8 v;            // in-flight tile (load() -> commit())
 
   DEVINL void init(const __bf16* __restrict__ dY, const ConvShape& cs,
@@ -632,13 +639,13 @@ struct DyBwdwStage {
       const long left = Ptot - p;
       if (left >= 8) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = src[(long)j * cs.K];
+        for (int j = 0; j < 8; ++j) v[j] = src[(long)j * cs.LDY];
       } else if (left > 0) {
-        for (int j = 0; j < (int)left; ++j) v[j] = src[(long)j * cs.K];
+        for (int j = 0; j < (int)left; ++j) v[j] = src[(long)j * cs.LDY];
       }
     }
     p += BK;
-    src += (long)BK * cs.K;
+    src += (long)BK * cs.LDY;
   }
 
   DEVINL void commit(__bf16* Sm) {
@@ -1013,7 +1020,7 @@ void launch_conv_fwd(const bf16_t* X, const bf16_t* W, const float* bias,
                        0, stream, (const __bf16*)X, (const __bf16*)W, bias,
                        (__bf16*)Y, ws, kc, cs);
     const long mk = M * K;
-    dim3 rgrid((unsigned)((mk / 4 + 255) / 256)), rblock(256);
+    dim3 rgrid((unsigned)(((mk + 3) / 4 + 255) / 256)), rblock(256);
 #define RL(BIASv, RELUv)                                                    \
     hipLaunchKernelGGL((conv_reduce_kernel<BIASv, RELUv>), rgrid, rblock,   \
                        0, stream, ws, bias, (__bf16*)Y, mk, K, zr)
@@ -1073,7 +1080,7 @@ void launch_conv_bwd_data(const bf16_t* dY, long ldy, const bf16_t* Wt,
     else BL(0);
 #undef BL
     const long mk = M * C;
-    dim3 rgrid((unsigned)((mk / 4 + 255) / 256)), rblock(256);
+    dim3 rgrid((unsigned)(((mk + 3) / 4 + 255) / 256)), rblock(256);
     hipLaunchKernelGGL((conv_reduce_kernel<false, false>), rgrid, rblock, 0,
                        stream, ws, nullptr, (__bf16*)dX, mk, C, zr);
     return;

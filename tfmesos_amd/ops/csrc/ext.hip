@@ -1441,6 +1441,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_bwd_data", &conv2d_bwd_data);
   m.def("conv2d_bwd_weight", &conv2d_bwd_weight);
   m.def("conv2d_bwd_weight_out", &conv2d_bwd_weight_out);
+  // reduction-slice heuristics (host only): tests assert which kernel
+  // path a shape takes, so a retuned gate cannot quietly unsplit them
+  m.def("conv_fwd_slices", &conv_fwd_slices, py::arg("N"), py::arg("K"),
+        py::arg("Ho"), py::arg("Wo"), py::arg("C"), py::arg("R"),
+        py::arg("S"));
+  m.def("conv_bwdd_slices", &conv_bwdd_slices, py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("C"), py::arg("K"), py::arg("R"),
+        py::arg("S"));
+  m.def("conv_bwdw_slices", &conv_bwdw_slices, py::arg("N"), py::arg("C"),
+        py::arg("K"), py::arg("R"), py::arg("S"), py::arg("Ho"),
+        py::arg("Wo"));
   bind_sparse(m);
   m.def("relu_bwd", &relu_bwd);
   m.def("colsum", &colsum, py::arg("x"), py::arg("out"));
