@@ -72,6 +72,131 @@ int vec_level(const void* base, long ld) {
   return 1;
 }
 
+// ---- GEMM plans: which kernels a call runs on and how K is sliced.
+// The bindings below call these, and gemm_plan / gemm_sgd_plan expose
+// them so a test can assert the path a shape takes.
+struct KSlices {
+  int kc = 0;       // k per slice, whole 32-k tiles (0: unsplit)
+  int nslice = 1;
+};
+
+// `want` slices rounded to whole BK tiles, which can leave fewer
+static KSlices k_slices(int K, int want) {
+  KSlices s;
+  if (want > 1) {
+    s.kc = ((K + want - 1) / want + 31) / 32 * 32;
+    s.nslice = (K + s.kc - 1) / s.kc;
+  }
+  return s;
+}
+
+// split-K when the plain tile grid can't feed the 256-CU chip and K
+// has enough depth to slice. colsum-fused GEMMs slice down to one BK
+// tile per slice (their K gate is the same — slicing SHALLOW colsum
+// GEMMs, mnist dW1 at K=100, measured slower: the second (reduce)
+// launch costs more than the occupancy it buys).
+static KSlices gemm_slices(int M, int N, int K, bool colsum, bool env) {
+  const int nx = (N + 63) / 64, ny = (M + 63) / 64;
+  if (nx * ny >= 256 || K < 256) return KSlices();
+  int want = std::min(colsum ? (K + 31) / 32 : K / 64, 256 / (nx * ny));
+  if (want > 16) want = 16;
+  if (env) {
+    static int want_env = -2;
+    if (want_env == -2) {
+      const char* e = getenv("TFA_SK_WANT");   // tuning override
+      want_env = e ? atoi(e) : -1;
+    }
+    if (want_env > 0) want = want_env;
+  }
+  return k_slices(K, want);
+}
+
+// gemm_sgd / gemm_sgd_pair: the plain slicing, no override
+static KSlices gemm_sgd_slices(int M, int N, int K) {
+  return gemm_slices(M, N, K, false, false);
+}
+
+enum GemmKernel { kGemmSmall, kGemmFwd1, kGemmTile, kGemmTileSk };
+enum GemmReduce { kRedNone, kRed1, kRed4, kRed4Cs, kRedLastArriver };
+struct GemmPlan {
+  GemmKernel kernel;
+  KSlices sk;
+  GemmReduce reduce;
+};
+
+// act: 0 none, 1 relu, 2 relu_bwd, 3 sub (2 and 3 carry aux); route as
+// in gemm_bias_act_impl. The argument combinations themselves are
+// checked there.
+static GemmPlan gemm_plan_of(int M, int N, int K, bool trans_a, bool trans_b,
+                             int act, bool colsum, int route) {
+  // small-tile ONE-kernel path for tiny tile grids (mnist fwd
+  // 100x100x784 and dW1 784x100x100): the 4 waves split K in-block
+  // (no split-K reduce pass — the second dispatch floor cost more
+  // than the whole GEMM at these sizes)
+  // gate: enough 32x32 tiles to feed the memory system (at 16 blocks
+  // the one-kernel form measured 16.5 us vs 11.1 for split-K + reduce
+  // on the mnist fwd shape — parallelism beats the saved dispatch
+  // floor there), few enough that the shape is in the tiny-GEMM
+  // regime, and K short enough that a wave's quarter is 1-2 chunks
+  const long stiles = (long)((M + 31) / 32) * ((N + 31) / 32);
+  if (act <= 1 && !trans_b && stiles >= 32 && stiles <= 512 && K <= 256)
+    return {kGemmSmall, KSlices(), kRedNone};
+  // not with the fused relu_bwd / sub epilogues — those stay
+  // single-phase
+  KSlices sk;
+  if (act <= 1) sk = gemm_slices(M, N, K, colsum, true);
+  // one-launch forward: the K slices become the waves of one workgroup
+  // (gemm_fwd1_kernel, bit-identical to stripes + reduce, so the gate
+  // is a speed decision only: outputs up to 128x128, where the stripes
+  // grid is at most 2x2 tiles and its reduce a second dispatch floor).
+  // TFA_GEMM_FWD1=0 restores the two-kernel path for A/B runs.
+  static int fwd1_on = -1;
+  if (fwd1_on < 0) {
+    const char* e = getenv("TFA_GEMM_FWD1");
+    fwd1_on = e ? (atoi(e) != 0) : 1;
+  }
+  const bool fwd1_fits = !trans_a && !trans_b && act <= 1 && !colsum &&
+                         sk.nslice > 1 && sk.nslice <= 16;
+  TORCH_CHECK(route != 2 || fwd1_fits,
+              "gemm: one-launch route needs nn, act none/relu, no aux, no "
+              "colsum and 2..16 K slices (got ", sk.nslice, ")");
+  if (route == 2 ||
+      (route == 0 && fwd1_on && fwd1_fits && M <= 128 && N <= 128))
+    return {kGemmFwd1, sk, kRedNone};
+  if (sk.nslice == 1) return {kGemmTile, sk, kRedNone};
+  GemmReduce red;
+  if (colsum) red = kRed4Cs;
+  else if (gemm_last_arriver(M, N, colsum, act)) red = kRedLastArriver;
+  else red = gemm_reduce_small((long)M * N) ? kRed1 : kRed4;
+  return {kGemmTileSk, sk, red};
+}
+
+std::tuple<std::string, long, long, std::string> gemm_plan(
+    long M, long N, long K, bool trans_a, bool trans_b, long act,
+    bool has_colsum, long route) {
+  TORCH_CHECK(M > 0 && N > 0 && K > 0 && act >= 0 && act <= 3 &&
+              route >= 0 && route <= 2, "gemm_plan: bad argument");
+  static const char* kn[] = {"small", "fwd1", "tile", "tile_sk"};
+  static const char* rn[] = {"none", "reduce1", "reduce4", "reduce4_cs",
+                             "last_arriver"};
+  const GemmPlan p = gemm_plan_of((int)M, (int)N, (int)K, trans_a, trans_b,
+                                  (int)act, has_colsum, (int)route);
+  return {kn[p.kernel], p.sk.kc, p.sk.nslice, rn[p.reduce]};
+}
+
+std::tuple<long, long> gemm_sgd_plan(long M, long N, long K) {
+  TORCH_CHECK(M > 0 && N > 0 && K > 0, "gemm_sgd_plan: bad argument");
+  const KSlices s = gemm_sgd_slices((int)M, (int)N, (int)K);
+  return {s.kc, s.nslice};
+}
+
+std::tuple<long, long> gemm_vec_levels(torch::Tensor a, torch::Tensor b) {
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.is_contiguous() &&
+              b.is_contiguous(), "gemm_vec_levels: contiguous 2-D");
+  return {vec_level(a.data_ptr(), a.size(1)),
+          vec_level(b.data_ptr(), b.size(1))};
+}
+
 // persistent per-device split-K workspace (one fp32 stripe per K-slice,
 // fully overwritten by every launch) + tile arrival counters (the
 // last-arriver epilogue resets them, so they stay zeroed between
@@ -158,87 +283,31 @@ torch::Tensor gemm_bias_act_impl(torch::Tensor a, torch::Tensor b,
                 "colsum_out must match out dtype, [N]");
     colsum_p = colsum_out.data_ptr();
   }
-  // small-tile ONE-kernel path for tiny tile grids (mnist fwd
-  // 100x100x784 and dW1 784x100x100): the 4 waves split K in-block
-  // (no split-K reduce pass — the second dispatch floor cost more
-  // than the whole GEMM at these sizes)
-  // gate: enough 32x32 tiles to feed the memory system (at 16 blocks
-  // the one-kernel form measured 16.5 us vs 11.1 for split-K + reduce
-  // on the mnist fwd shape — parallelism beats the saved dispatch
-  // floor there), few enough that the shape is in the tiny-GEMM
-  // regime, and K short enough that a wave's quarter is 1-2 chunks
-  const long stiles = (long)((M + 31) / 32) * ((N + 31) / 32);
-  const bool cs_small_ok =
-      colsum_p == nullptr ||
-      (trans_a && !trans_b && bias_p == nullptr && act == 0 &&
-       colsum_out.scalar_type() == out.scalar_type());
-  if (act <= 1 && !trans_b && aux_p == nullptr && cs_small_ok &&
-      stiles >= 32 && stiles <= 512 && Ka <= 256) {
+  // kernel path and K slicing: see gemm_plan_of
+  const GemmPlan plan = gemm_plan_of(M, N, Ka, trans_a, trans_b, (int)act,
+                                     colsum_p != nullptr, (int)route);
+  const int veca = vec_level(a.data_ptr(), a.size(1));
+  const int vecb = vec_level(b.data_ptr(), b.size(1));
+  if (plan.kernel == kGemmSmall) {
     launch_gemm_small((const bf16_t*)a.data_ptr(),
                       (const bf16_t*)b.data_ptr(), bias_p, bias_bf16,
                       out.data_ptr(), out_f32, act == 1 ? 1 : 0, colsum_p,
                       out_f32, M, N, Ka, a.size(1), b.size(1), N, trans_a,
-                      nullptr, cur_stream());
+                      veca, vecb, nullptr, cur_stream());
     return out;
   }
-  // split-K when the plain tile grid can't feed the 256-CU chip and K
-  // has enough depth to slice (any transpose combo; not with the
-  // fused colsum/relu_bwd epilogues — those stay single-phase)
-  const int nx = (N + 63) / 64, ny = (M + 63) / 64;
-  int nslice = 1, kc = 0;
-  float* ws = nullptr;
-  int* cnt = nullptr;
-  // colsum-fused GEMMs (tn, no bias/act) can slice too: partials go to
-  // an extra [nslice, N] stripe area reduced in phase 2. Same K gate as
-  // plain shapes — slicing SHALLOW colsum GEMMs (mnist dW1, K=100)
-  // measured slower: the second (reduce) launch costs more than the
-  // occupancy it buys.
-  const bool cs_ok = colsum_p == nullptr ||
-                     (trans_a && !trans_b && bias_p == nullptr && act == 0);
-  const long kmin = 256;
-  if (act <= 1 && cs_ok && nx * ny < 256 && Ka >= kmin) {
-    int want = std::min(colsum_p != nullptr ? (int)((Ka + 31) / 32)
-                                            : (int)(Ka / 64),
-                        256 / (nx * ny));
-    if (want > 16) want = 16;
-    static int want_env = -2;
-    if (want_env == -2) {
-      const char* e = getenv("TFA_SK_WANT");   // tuning override
-      want_env = e ? atoi(e) : -1;
-    }
-    if (want_env > 0) want = want_env;
-    if (want > 1) {
-      kc = ((Ka + want - 1) / want + 31) / 32 * 32;
-      nslice = (Ka + kc - 1) / kc;
-    }
-  }
-  // one-launch forward: the K slices become the waves of one workgroup
-  // (gemm_fwd1_kernel, bit-identical to stripes + reduce, so the gate
-  // is a speed decision only: outputs up to 128x128, where the stripes
-  // grid is at most 2x2 tiles and its reduce a second dispatch floor).
-  // TFA_GEMM_FWD1=0 restores the two-kernel path for A/B runs.
-  static int fwd1_on = -1;
-  if (fwd1_on < 0) {
-    const char* e = getenv("TFA_GEMM_FWD1");
-    fwd1_on = e ? (atoi(e) != 0) : 1;
-  }
-  const bool fwd1_fits = !trans_a && !trans_b && act <= 1 &&
-                         aux_p == nullptr && colsum_p == nullptr &&
-                         nslice > 1 && nslice <= 16;
-  TORCH_CHECK(route != 2 || fwd1_fits,
-              "gemm: one-launch route needs nn, act none/relu, no aux, no "
-              "colsum and 2..16 K slices (got ", nslice, ")");
-  if (route == 2 ||
-      (route == 0 && fwd1_on && fwd1_fits && M <= 128 && N <= 128)) {
+  const int nslice = plan.sk.nslice, kc = plan.sk.kc;
+  if (plan.kernel == kGemmFwd1) {
     launch_gemm_fwd1((const bf16_t*)a.data_ptr(),
                      (const bf16_t*)b.data_ptr(), bias_p, bias_bf16,
                      out.data_ptr(), out_f32, act == 1 ? 1 : 0, kc, nslice,
-                     M, N, Ka, a.size(1), b.size(1), N,
-                     vec_level(a.data_ptr(), a.size(1)),
-                     vec_level(b.data_ptr(), b.size(1)), (int)variant, snap,
-                     snap_taken, cur_stream());
+                     M, N, Ka, a.size(1), b.size(1), N, veca, vecb,
+                     (int)variant, snap, snap_taken, cur_stream());
     return out;
   }
+  const int nx = (N + 63) / 64, ny = (M + 63) / 64;
+  float* ws = nullptr;
+  int* cnt = nullptr;
   if (nslice > 1)
     ws = splitk_ws(a.device(),
                    (long)M * N * nslice +
@@ -247,9 +316,7 @@ torch::Tensor gemm_bias_act_impl(torch::Tensor a, torch::Tensor b,
   launch_gemm((const bf16_t*)a.data_ptr(), (const bf16_t*)b.data_ptr(),
               bias_p, bias_bf16, out.data_ptr(), out_f32, aux_p, colsum_p,
               ws, cnt, kc, nslice, M, N, Ka, a.size(1), b.size(1), N,
-              trans_a, trans_b, (int)act,
-              vec_level(a.data_ptr(), a.size(1)),
-              vec_level(b.data_ptr(), b.size(1)), cur_stream(), snap,
+              trans_a, trans_b, (int)act, veca, vecb, cur_stream(), snap,
               snap_taken);
   return out;
 }
@@ -333,15 +400,8 @@ void gemm_sgd(torch::Tensor a, torch::Tensor b, bool trans_a, bool trans_b,
     shp = (bf16_t*)shadow.data_ptr();
   }
   const int nx = (N + 63) / 64, ny = (M + 63) / 64;
-  int nslice = 1, kc = 0;
-  if (nx * ny < 256 && Ka >= 256) {
-    int want = std::min((int)(Ka / 64), 256 / (nx * ny));
-    if (want > 16) want = 16;
-    if (want > 1) {
-      kc = ((Ka + want - 1) / want + 31) / 32 * 32;
-      nslice = (Ka + kc - 1) / kc;
-    }
-  }
+  const KSlices sk = gemm_sgd_slices(M, N, Ka);
+  const int nslice = sk.nslice, kc = sk.kc;
   if (nslice > 1) {
     int* cnt_unused;
     float* ws = splitk_ws(a.device(), (long)M * N * nslice,
@@ -394,17 +454,11 @@ void gemm_sgd_pair(torch::Tensor a1, torch::Tensor b1, bool ta1, bool tb1,
     TORCH_CHECK(x.p.is_contiguous() &&
                 x.p.scalar_type() == torch::kFloat32 &&
                 x.p.numel() == (long)x.M * x.N, "gemm_sgd_pair: bad param");
-    const int nx = (x.N + 63) / 64, ny = (x.M + 63) / 64;
-    x.nslice = 1;
-    x.kc = 0;
-    if (nx * ny < 256 && x.K >= 256) {
-      int want = std::min((int)(x.K / 64), 256 / (nx * ny));
-      if (want > 16) want = 16;
-      if (want > 1) {
-        x.kc = ((x.K + want - 1) / want + 31) / 32 * 32;
-        x.nslice = (x.K + x.kc - 1) / x.kc;
-      }
-    }
+    const KSlices sk = gemm_sgd_slices(x.M, x.N, x.K);
+    x.nslice = sk.nslice;
+    x.kc = sk.kc;
+    // an arbitrary element offset for the second half: the reduce
+    // checks its stripe base before it takes vector loads
     x.ws_off = ws_total;
     if (x.nslice > 1) ws_total += (long)x.M * x.N * x.nslice;
   }
@@ -1247,7 +1301,9 @@ void mlp_tail_sgd(torch::Tensor x, torch::Tensor dh,
                     (const bf16_t*)dh.data_ptr(), nullptr, false,
                     nullptr, false, 0, nullptr, false,
                     M, N, B, (int)x.size(1), (int)dh.size(1), N,
-                    /*ta=*/true, &sga, cur_stream());
+                    /*ta=*/true, vec_level(x.data_ptr(), x.size(1)),
+                    vec_level(dh.data_ptr(), dh.size(1)), &sga,
+                    cur_stream());
 }
 
 // Shared argument checks of the fused head+tail ops: the limits of the
@@ -1434,6 +1490,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlp_fwd_snap", &mlp_fwd_snap);
   m.def("mlp_head_tail_grads", &mlp_head_tail_grads);
   m.def("gemm_sgd_pair", &gemm_sgd_pair);
+  // the kernel path, K slicing and staging level a GEMM call takes
+  // (the functions the calls themselves use), for tests
+  m.def("gemm_plan", &gemm_plan, py::arg("M"), py::arg("N"), py::arg("K"),
+        py::arg("trans_a"), py::arg("trans_b"), py::arg("act"),
+        py::arg("has_colsum"), py::arg("route"));
+  m.def("gemm_sgd_plan", &gemm_sgd_plan, py::arg("M"), py::arg("N"),
+        py::arg("K"));
+  m.def("gemm_vec_levels", &gemm_vec_levels, py::arg("a"), py::arg("b"));
   m.def("add_n", &add_n);
   m.def("bn_group_bwd_multi", &bn_group_bwd_multi);
   m.def("maxpool3x3s2_bwd", &maxpool3x3s2_bwd);

@@ -261,6 +261,9 @@ void gemm_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B,
       // (the one-WG-consumer trap, see mlp.py's FROMWS note)
       const int crow = t >> 2;             // 0..63 within tile
       const int ccol0 = (t & 3) * 16;      // 4 f32x4 groups per row
+      // z2*M*ldc + row*ldc + col (col % 4 == 0) is 16-byte aligned for
+      // every row and stripe only when ldc % 4 == 0 and the base is
+      const bool vec4 = (ldc & 3) == 0 && ((uintptr_t)ws & 15) == 0;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int row = tm0 + crow;
@@ -270,7 +273,7 @@ void gemm_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B,
         f32x4 v = {};
         for (int z2 = 0; z2 < ns; ++z2) {
           const float* s2 = &ws[(long)z2 * M * ldc + idx];
-          if (col + 4 <= N) {
+          if (vec4 && col + 4 <= N) {
             v += *(const f32x4*)s2;
           } else {
             for (int j = 0; j < 4; ++j)
@@ -361,6 +364,17 @@ void splitk_reduce_small_kernel(const float* __restrict__ ws,
   else ((__bf16*)Cout)[i] = (__bf16)v;
 }
 
+// f32x4 stripe loads at ws + z*mn + i0 (i0 % 4 == 0) are 16-byte aligned
+// for every slice z only when mn % 4 == 0 and the stripe base is: an odd
+// mn puts every other stripe off the boundary, and gemm_sgd_pair hands
+// its second half a base that is an arbitrary element offset into the
+// shared workspace. Otherwise the same elements are loaded one by one,
+// summed in the same order. With mn % 4 == 0 a thread's four elements
+// are all inside mn, so the vector path needs no tail.
+DEVINL bool stripes_vec4(const float* ws, long mn) {
+  return (mn & 3) == 0 && ((uintptr_t)ws & 15) == 0;
+}
+
 template <int ACT, bool BIAS, bool OUTF32>
 __global__ __launch_bounds__(256)
 void splitk_reduce_kernel(const float* __restrict__ ws, const void* __restrict__ bias,
@@ -381,15 +395,18 @@ void splitk_reduce_kernel(const float* __restrict__ ws, const void* __restrict__
       else ((__bf16*)cs_out)[n] = (__bf16)s;
     }
   }
+  const bool vec4 = stripes_vec4(ws, mn);
   f32x4 v = {};
   for (int z = 0; z < nslice; ++z) {
     const float* s = ws + (long)z * mn + i0;
-    if (i0 + 4 <= mn) {
+    if (vec4) {
       const f32x4 sv = *(const f32x4*)s;
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] += sv[j];
     } else {
-      for (int j = 0; i0 + j < mn; ++j) v[j] += s[j];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (i0 + j < mn) v[j] += s[j];
     }
   }
 #pragma unroll
@@ -840,7 +857,7 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
                        void* __restrict__ Cout, bool out_f32, int relu,
                        void* __restrict__ colsum_out, bool cs_f32,
                        int M, int N, int K, int lda, int ldb, int ldc,
-                       SmallSgd sg) {
+                       int veca, int vecb, SmallSgd sg) {
   // wave-private 32x32 images, stride exactly 32 + the sptr chunk
   // swizzle: the transposing operands (A when TA, B always) store
   // K-MAJOR [k][col] — commit is two b128 stores (the transposed
@@ -862,8 +879,11 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
   __bf16* Bw = Bs[w];
   const int kk = lane & 31;
   const int half = lane >> 5;
-  const bool av = (lda & 7) == 0;   // bf16x8-aligned rows
-  const bool bv = (ldb & 7) == 0;
+  // bf16x8-aligned rows: pitch AND base (vec_level, as gemm_kernel) —
+  // an operand that is a view into its storage has an aligned pitch
+  // and a base that is not
+  const bool av = veca == 8;
+  const bool bv = vecb == 8;
   f32x4 acc[4] = {};
   float csp[16] = {};
   bf16x8 ra0, ra1, rb0, rb1;        // in-flight chunk (load -> commit)
@@ -1527,15 +1547,18 @@ void splitk_reduce_sgd_kernel(const float* __restrict__ ws, int nslice,
                               float lr, float gscale, float nd) {
   const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i0 >= mn) return;
+  const bool vec4 = stripes_vec4(ws, mn);
   f32x4 v = {};
   for (int z = 0; z < nslice; ++z) {
     const float* sp = ws + (long)z * mn + i0;
-    if (i0 + 4 <= mn) {
+    if (vec4) {
       const f32x4 sv = *(const f32x4*)sp;
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] += sv[j];
     } else {
-      for (int j = 0; i0 + j < mn; ++j) v[j] += sp[j];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (i0 + j < mn) v[j] += sp[j];
     }
   }
 #pragma unroll
@@ -1552,6 +1575,27 @@ void splitk_reduce_sgd_kernel(const float* __restrict__ ws, int nslice,
 }
 
 }  // namespace
+
+// last-arriver epilogue: MEASURED DEAD END on the mnist fwd shape
+// (4 tiles x 9 slices): the 4 consumer blocks pull the stripes
+// cross-XCD through the release/acquire fences and the fwd GEMM
+// went 8.2 -> 48 us scalar / ~20 us vectorized, vs 12.9 us for
+// stripes + the wide reduce kernel. Same lesson as the FROMWS head:
+// few-WG consumers must not read many-XCD-producer output. Kept
+// behind TFA_GEMM_LA=1 for re-measurement; default off.
+bool gemm_last_arriver(int M, int N, bool colsum, int act) {
+  static int la_on = -1;
+  if (la_on < 0) {
+    const char* e = getenv("TFA_GEMM_LA");
+    la_on = e ? atoi(e) : 0;
+  }
+  return la_on && !colsum && act <= 1 &&
+         (long)ceil_div(N, BN) * ceil_div(M, BM) <= 64;
+}
+
+// stripe reduce of SMALL outputs: 1 elem/thread (see
+// splitk_reduce_small_kernel), else 4
+bool gemm_reduce_small(long mn) { return mn <= (1 << 16); }
 
 void launch_gemm(const bf16_t* A, const bf16_t* B, const void* bias,
                  bool bias_bf16, void* C, bool out_f32, const bf16_t* aux,
@@ -1570,21 +1614,7 @@ void launch_gemm(const bf16_t* A, const bf16_t* B, const void* bias,
   const bool cs = colsum_out != nullptr;
   const int rflags = (act == 1 ? 1 : 0) | (out_f32 ? 2 : 0) |
                      (has_bias ? 4 : 0);
-  // last-arriver epilogue: MEASURED DEAD END on the mnist fwd shape
-  // (4 tiles x 9 slices): the 4 consumer blocks pull the stripes
-  // cross-XCD through the release/acquire fences and the fwd GEMM
-  // went 8.2 -> 48 us scalar / ~20 us vectorized, vs 12.9 us for
-  // stripes + the wide reduce kernel. Same lesson as the FROMWS head:
-  // few-WG consumers must not read many-XCD-producer output. Kept
-  // behind TFA_GEMM_LA=1 for re-measurement; default off.
-  static int la_on = -1;
-  if (la_on < 0) {
-    const char* e = getenv("TFA_GEMM_LA");
-    la_on = e ? atoi(e) : 0;
-  }
-  if (!la_on || cs || act > 1 ||
-      (long)ceil_div(N, BN) * ceil_div(M, BM) > 64)
-    cnt = nullptr;
+  if (!gemm_last_arriver(M, N, cs, act)) cnt = nullptr;
 #define LAUNCH(TAv, TBv, ACTv, BIASv, OUTv, SKv, CSv)                       \
   hipLaunchKernelGGL((gemm_kernel<TAv, TBv, ACTv, BIASv, OUTv, SKv, CSv>),  \
                      grid, block, 0, stream, (const __bf16*)A,              \
@@ -1639,7 +1669,7 @@ void launch_gemm(const bf16_t* A, const bf16_t* B, const void* bias,
     // phase 2: fixed-order stripe reduce + fused epilogue (small
     // outputs: 1 elem/thread for 4x the workgroups)
     const long mn = (long)M * ldc;
-    const bool small_r = mn <= (1 << 16);
+    const bool small_r = gemm_reduce_small(mn);
     dim3 rgrid((unsigned)(small_r ? (mn + 255) / 256
                                   : ((mn + 3) / 4 + 255) / 256));
     dim3 rblock(256);
@@ -1742,8 +1772,9 @@ void launch_gemm_fwd1(const bf16_t* A, const bf16_t* B, const void* bias,
 void launch_gemm_small(const bf16_t* A, const bf16_t* B, const void* bias,
                        bool bias_bf16, void* C, bool out_f32, int relu,
                        void* colsum_out, bool cs_f32, int M, int N, int K,
-                       int lda, int ldb, int ldc, bool ta,
-                       const SmallSgdArgs* sga, hipStream_t stream) {
+                       int lda, int ldb, int ldc, bool ta, int veca,
+                       int vecb, const SmallSgdArgs* sga,
+                       hipStream_t stream) {
   dim3 grid(ceil_div(M, 32), ceil_div(N, 32)), block(256);
   SmallSgd sg = {};
   if (sga) {
@@ -1760,7 +1791,7 @@ void launch_gemm_small(const bf16_t* A, const bf16_t* B, const void* bias,
   hipLaunchKernelGGL((gemm_small_kernel<TAv, CSv>), grid, block, 0,         \
                      stream, (const __bf16*)A, (const __bf16*)B, bias,      \
                      bias_bf16, C, out_f32, relu, colsum_out, cs_f32, M, N, \
-                     K, lda, ldb, ldc, sg)
+                     K, lda, ldb, ldc, veca, vecb, sg)
   if (ta) { if (cs) GS(true, true); else GS(true, false); }
   else    { if (cs) GS(false, true); else GS(false, false); }
 #undef GS
