@@ -55,7 +55,7 @@ def parse_args(argv):
     p.add_argument("--learning_rate", type=float, default=0.01)
     p.add_argument("--sync_replicas", action="store_true")
     p.add_argument("--optimizer", default="sgd",
-                   help="sgd|adam|adagrad (reference used Adam)")
+                   help="sgd|adam|adagrad|ftrl_proximal (reference used Adam)")
     p.add_argument("--checkpoint", default=None,
                    help="save PS state here at the end; resume if present")
     return p.parse_args(argv)

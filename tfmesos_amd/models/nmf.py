@@ -80,7 +80,8 @@ class SparseNMF(object):
     the minibatch Frobenius gradient on MFMA GEMMs, and pushes sparse
     row grads back (HIP gather/scatter-add on a GPU PS).
     ``optimizer`` / ``opt_hparams`` select the tables' sparse optimizer
-    (EmbeddingTable: sgd, adagrad, adam); the default is plain SGD.
+    (EmbeddingTable: sgd, adagrad, adam, ftrl_proximal); the default is
+    plain SGD.
     """
 
     def __init__(self, rank, world, device="cpu", n=1000, factor_rank=200,

@@ -9,10 +9,10 @@ numerics tests compare HIP kernel output against these references.
 
 Op inventory mirrors what the reference delegated to TensorFlow's PS
 runtime: fused optimizer apply (SGD/momentum, Adagrad,
-Adam), bf16 GEMM with fused bias+ReLU epilogue, fused softmax
+Adam, FTRL-Proximal), bf16 GEMM with fused bias+ReLU epilogue, fused softmax
 cross-entropy, embedding gather / scatter-add, fused sparse optimizer
-apply for embedding rows (sparse_sgd / sparse_adagrad / sparse_adam —
-TF's SparseApply*: duplicates summed, one update per touched row), and
+apply for embedding rows (sparse_sgd / sparse_adagrad / sparse_adam /
+sparse_ftrl — TF's SparseApply*: duplicates summed, one update per touched row), and
 pooled (bag) lookups: embedding_bag forward (TF's embedding_lookup_sparse,
 combiner sum / mean, optional weights) and the same sparse applies fed
 bag gradients (``offsets=``); and the routing of requests to a row-sharded
@@ -136,6 +136,74 @@ def fused_adagrad(param, grad, accum, lr, eps=1e-10, weight_decay=0.0,
         g = g + weight_decay * param
     accum.addcmul_(g, g, value=1.0)
     param.addcdiv_(g, accum.sqrt().add_(eps), value=-lr)
+    if bf16_out is not None:
+        bf16_out.copy_(param.to(torch.bfloat16))
+
+
+def _ftrl_check(lr, l1, l2, acc0):
+    if not lr > 0 or not l1 >= 0 or not l2 >= 0 or not acc0 > 0:
+        raise ValueError("ftrl_proximal needs lr > 0, l1 >= 0, l2 >= 0 and "
+                         "initial_accumulator_value > 0, got lr=%r, l1=%r, "
+                         "l2=%r, initial_accumulator_value=%r"
+                         % (lr, l1, l2, acc0))
+
+
+@torch.no_grad()
+def fused_ftrl(param, grad, accum, linear, lr, l1=0.0, l2=0.0,
+               initial_accumulator_value=0.1, bf16_out=None, grad_scale=1.0):
+    """In-place FTRL-Proximal (TF's FtrlOptimizer, lr_power -0.5) on an fp32
+    master param: per-coordinate adaptive steps, l1 gives weights that are
+    exactly 0.0, l2 is the only regulariser (no weight decay, no l2
+    shrinkage). Per element, all in fp32 in this order, constants rounded
+    to fp32 first, sign(0) = 0::
+
+        gv = grad * grad_scale
+        if accum == 0 and linear == 0:      # never updated: seed linear
+            linear = -(p * (sqrt(acc0)/lr + 2*l2) + sign(p)*l1)
+        n_new = accum + gv*gv
+        s_old = sqrt(accum + acc0);  s_new = sqrt(n_new + acc0)
+        sigma = (s_new - s_old) / lr
+        z     = linear + (gv - sigma*p)
+        quad  = s_new/lr + 2*l2
+        p     = (sign(z)*l1 - z)/quad  if |z| > l1  else +0.0
+        accum = n_new;  linear = z
+
+    accum holds the sum of squared gradients only: acc0 =
+    initial_accumulator_value is added on read and never stored, so both
+    state tensors START AS ZEROS. FTRL's weight is a pure function of its
+    state; the seeding step makes the current weight of a never-updated
+    element (a table's random initial row) the FTRL solution instead of
+    throwing it away on the first touch, so this is not bit for bit TF's
+    Ftrl and its name here is "ftrl_proximal". GPU: csrc/ftrl.h in
+    csrc/apply.hip, shadow written in the same pass."""
+    acc0 = initial_accumulator_value
+    _ftrl_check(lr, l1, l2, acc0)
+    if param.is_cuda:
+        _ext().fused_ftrl(param, grad, accum, linear,
+                          bf16_out if bf16_out is not None
+                          else torch.empty(0, dtype=torch.bfloat16,
+                                           device=param.device),
+                          float(lr), float(l1), float(l2), float(acc0),
+                          float(grad_scale))
+        return
+    # constants as full fp32 tensors: torch divides by a one-element operand
+    # through its reciprocal, which is not the correctly rounded quotient
+    def f32(x):
+        return torch.full(param.shape, float(x), dtype=torch.float32)
+    lr, l1, l2, acc0 = f32(lr), f32(l1), f32(l2), f32(acc0)
+    two_l2 = 2 * l2
+    gv = grad.float() * f32(grad_scale)
+    seed = -(param * (acc0.sqrt() / lr + two_l2) + torch.sign(param) * l1)
+    lin = torch.where((accum == 0) & (linear == 0), seed, linear)
+    n_new = accum + gv * gv
+    s_new = (n_new + acc0).sqrt()
+    sigma = (s_new - (accum + acc0).sqrt()) / lr
+    z = lin + (gv - sigma * param)
+    quad = s_new / lr + two_l2
+    param.copy_(torch.where(z.abs() > l1, (torch.sign(z) * l1 - z) / quad,
+                            torch.zeros_like(z)))
+    accum.copy_(n_new)
+    linear.copy_(z)
     if bf16_out is not None:
         bf16_out.copy_(param.to(torch.bfloat16))
 
@@ -1309,11 +1377,15 @@ def hash_init_new_rows(keys, rows, is_new, master, shadow, states, seed,
 # expanded rows are never built); the CPU reference builds them.
 
 _SPARSE_SGD, _SPARSE_SGD_MOM, _SPARSE_ADAGRAD, _SPARSE_ADAM = 0, 1, 2, 3
+_SPARSE_FTRL = 4
 
 
 def _sparse_hip(code, param, ids, grads, s1, s2, bf16_out, step, lr, beta1,
-                beta2, eps, weight_decay, grad_scale, bag=None):
+                beta2, eps, weight_decay, grad_scale, bag=None,
+                ftrl=(0.0, 0.0, 0.1)):
+    """ftrl: (l1, l2, initial_accumulator_value), read by _SPARSE_FTRL."""
     dev = param.device
+    l1, l2, acc0 = (float(x) for x in ftrl)
     ef = torch.empty(0, device=dev)
     if bag is not None:
         offsets, weights, combiner = bag
@@ -1324,7 +1396,8 @@ def _sparse_hip(code, param, ids, grads, s1, s2, bf16_out, step, lr, beta1,
             bf16_out if bf16_out is not None
             else torch.empty(0, dtype=torch.bfloat16, device=dev),
             code, int(step), combiner == "mean", float(lr), float(beta1),
-            float(beta2), float(eps), float(weight_decay), float(grad_scale))
+            float(beta2), float(eps), float(weight_decay), float(grad_scale),
+            l1, l2, acc0)
         return
     _ext().sparse_apply(
         param, ids, grads, s1 if s1 is not None else ef,
@@ -1332,7 +1405,7 @@ def _sparse_hip(code, param, ids, grads, s1, s2, bf16_out, step, lr, beta1,
         bf16_out if bf16_out is not None
         else torch.empty(0, dtype=torch.bfloat16, device=dev),
         code, int(step), float(lr), float(beta1), float(beta2), float(eps),
-        float(weight_decay), float(grad_scale))
+        float(weight_decay), float(grad_scale), l1, l2, acc0)
 
 
 def _bag_of_call(ids, grads, offsets, weights, combiner):
@@ -1446,6 +1519,33 @@ def sparse_adam(param, ids, grads, exp_avg, exp_avg_sq, step, lr,
         fused_adam(p, g, m, v, step, lr, beta1=beta1, beta2=beta2, eps=eps,
                    weight_decay=weight_decay, grad_scale=grad_scale)
     _sparse_cpu(param, ids, grads, [exp_avg, exp_avg_sq], bf16_out, dense)
+
+
+@torch.no_grad()
+def sparse_ftrl(param, ids, grads, accum, linear, lr, l1=0.0, l2=0.0,
+                initial_accumulator_value=0.1, bf16_out=None, grad_scale=1.0,
+                *, offsets=None, weights=None, combiner="sum"):
+    """Sparse FTRL-Proximal: the rule of ``fused_ftrl`` once per touched
+    row on its summed gradient; accum and linear ([V,D], zeros at the
+    start) move only on touched rows. A touched row whose summed gradient
+    is zero (ids [3,3] with grads g,-g) keeps its weights up to rounding
+    but gets its linear term seeded. With ``offsets``: a pooled push,
+    grads [B,D] bag gradients."""
+    acc0 = initial_accumulator_value
+    _ftrl_check(lr, l1, l2, acc0)
+    bag = _bag_of_call(ids, grads, offsets, weights, combiner)
+    if param.is_cuda:
+        _sparse_hip(_SPARSE_FTRL, param, ids, grads, accum, linear, bf16_out,
+                    1, lr, 0.0, 0.0, 0.0, 0.0, grad_scale, bag=bag,
+                    ftrl=(l1, l2, acc0))
+        return
+    if bag is not None:
+        grads = _bag_rows_cpu(ids, grads, bag)
+
+    def step(p, g, a, c):
+        fused_ftrl(p, g, a, c, lr, l1=l1, l2=l2,
+                   initial_accumulator_value=acc0, grad_scale=grad_scale)
+    _sparse_cpu(param, ids, grads, [accum, linear], bf16_out, step)
 
 
 # --------------------------------------------------------------- relu bwd

@@ -16,3 +16,8 @@ void launch_adam(float* p, const void* g, bool g_bf16, float* m, float* v,
 void launch_adagrad(float* p, const void* g, bool g_bf16, float* acc,
                     bf16_t* pbf, long n, float lr, float eps, float wd,
                     float gscale, hipStream_t stream);
+// FTRL-Proximal (ftrl.h): acc = accumulator, lin = linear term, acc0 =
+// initial_accumulator_value (added on read, never stored).
+void launch_ftrl(float* p, const void* g, bool g_bf16, float* acc, float* lin,
+                 bf16_t* pbf, long n, float lr, float l1, float l2,
+                 float acc0, float gscale, hipStream_t stream);

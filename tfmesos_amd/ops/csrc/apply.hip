@@ -9,6 +9,7 @@
 // float4-vectorized, grid sized to fill 256 CUs when the buffer is large.
 #include "common.h"
 #include "apply.h"
+#include "ftrl.h"
 
 namespace {
 
@@ -169,6 +170,45 @@ __global__ void adagrad_kernel(float* __restrict__ p, const G* __restrict__ g,
   }
 }
 
+// FTRL-Proximal (the rule of ftrl.h): acc = accumulator, lin = linear term.
+template <typename G, bool BF16OUT>
+__global__ void ftrl_kernel(float* __restrict__ p, const G* __restrict__ g,
+                            float* __restrict__ acc, float* __restrict__ lin,
+                            bf16_t* __restrict__ pbf, long n, FtrlHp hp) {
+  long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  long stride = (long)gridDim.x * blockDim.x * 4;
+  long i = i0;
+  for (; i + 4 <= n; i += stride) {
+    const f32x4 gv = load_g4(g, i);
+    f32x4 pv = *(const f32x4*)&p[i];
+    f32x4 a = *(const f32x4*)&acc[i];
+    f32x4 c = *(const f32x4*)&lin[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = pv[j], aj = a[j], cj = c[j];
+      ftrl_elem(pj, aj, cj, gv[j], hp);
+      pv[j] = pj, a[j] = aj, c[j] = cj;
+    }
+    *(f32x4*)&acc[i] = a;
+    *(f32x4*)&lin[i] = c;
+    *(f32x4*)&p[i] = pv;
+    if (BF16OUT) {
+      bf16x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = (__bf16)pv[j];
+      *(bf16x4*)&((__bf16*)pbf)[i] = o;
+    }
+  }
+  for (; i < n; ++i) {
+    float pv = p[i], a = acc[i], c = lin[i];
+    ftrl_elem(pv, a, c, load_g(g, i), hp);
+    acc[i] = a;
+    lin[i] = c;
+    p[i] = pv;
+    if (BF16OUT) pbf[i] = f2bf(pv);
+  }
+}
+
 inline dim3 apply_grid(long n) {
   // >=2048 workgroups fills 256 CUs x 8 blocks; small buffers get fewer
   long blocks = (n / 4 + 255) / 256;
@@ -220,6 +260,19 @@ void launch_adagrad(float* p, const void* g, bool g_bf16, float* acc,
 #define DISP(GT, OUTV)                                                    \
   hipLaunchKernelGGL((adagrad_kernel<GT, OUTV>), grid, block, 0, stream,  \
                      p, (const GT*)g, acc, pbf, n, lr, eps, wd, gscale)
+  if (g_bf16) { if (pbf) DISP(bf16_t, true); else DISP(bf16_t, false); }
+  else        { if (pbf) DISP(float, true); else DISP(float, false); }
+#undef DISP
+}
+
+void launch_ftrl(float* p, const void* g, bool g_bf16, float* acc, float* lin,
+                 bf16_t* pbf, long n, float lr, float l1, float l2,
+                 float acc0, float gscale, hipStream_t stream) {
+  dim3 grid = apply_grid(n), block(256);
+  const FtrlHp hp = {lr, l1, l2, acc0, gscale};
+#define DISP(GT, OUTV)                                                  \
+  hipLaunchKernelGGL((ftrl_kernel<GT, OUTV>), grid, block, 0, stream, p, \
+                     (const GT*)g, acc, lin, pbf, n, hp)
   if (g_bf16) { if (pbf) DISP(bf16_t, true); else DISP(bf16_t, false); }
   else        { if (pbf) DISP(float, true); else DISP(float, false); }
 #undef DISP

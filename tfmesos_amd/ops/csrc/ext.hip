@@ -64,6 +64,34 @@ void fused_adagrad(torch::Tensor param, torch::Tensor grad,
                  (float)weight_decay, (float)grad_scale, cur_stream());
 }
 
+// FTRL-Proximal (csrc/ftrl.h): accum = sum of squared gradients, linear =
+// the linear term; both start at zero.
+void fused_ftrl(torch::Tensor param, torch::Tensor grad, torch::Tensor accum,
+                torch::Tensor linear, torch::Tensor bf16_out, double lr,
+                double l1, double l2, double initial_accumulator_value,
+                double grad_scale) {
+  long n = param.numel();
+  TORCH_CHECK(param.is_cuda() && param.is_contiguous() &&
+              param.scalar_type() == torch::kFloat32 && grad.numel() == n,
+              "ftrl: param must be contiguous fp32 on GPU, grad its size");
+  TORCH_CHECK(lr > 0 && l1 >= 0 && l2 >= 0 && initial_accumulator_value > 0,
+              "ftrl: need lr > 0, l1 >= 0, l2 >= 0, "
+              "initial_accumulator_value > 0");
+  float* acc = opt_f32(accum, n, "accum");
+  float* lin = opt_f32(linear, n, "linear");
+  TORCH_CHECK(acc != nullptr && lin != nullptr && accum.is_contiguous() &&
+              linear.is_contiguous(),
+              "ftrl: accum and linear must be contiguous fp32 of param's "
+              "size");
+  if (n == 0) return;   // a zero-size grid is a launch error
+  bool gb;
+  const void* g = grad_ptr(grad, &gb);
+  launch_ftrl(param.data_ptr<float>(), g, gb, acc, lin,
+              opt_bf16(bf16_out, n, "bf16_out"), n, (float)lr, (float)l1,
+              (float)l2, (float)initial_accumulator_value, (float)grad_scale,
+              cur_stream());
+}
+
 // staging vector width for an operand: b128 when every row start stays
 // 16B-aligned, b32 when 4B, else scalar
 int vec_level(const void* base, long ld) {
@@ -1464,6 +1492,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("param"), py::arg("grad"), py::arg("accum"),
         py::arg("bf16_out"), py::arg("lr"), py::arg("eps") = 1e-10,
         py::arg("weight_decay") = 0.0, py::arg("grad_scale") = 1.0);
+  m.def("fused_ftrl", &fused_ftrl, "fused FTRL-Proximal apply + bf16 shadow",
+        py::arg("param"), py::arg("grad"), py::arg("accum"),
+        py::arg("linear"), py::arg("bf16_out"), py::arg("lr"),
+        py::arg("l1") = 0.0, py::arg("l2") = 0.0,
+        py::arg("initial_accumulator_value") = 0.1,
+        py::arg("grad_scale") = 1.0);
   m.def("gemm_bias_act", &gemm_bias_act, "bf16 MFMA GEMM + bias + act");
   m.def("gemm_bias_act_route", &gemm_bias_act_route);
   m.def("gemm_bias_act_out", &gemm_bias_act_out,

@@ -67,7 +67,8 @@ void embedding_scatter_add(torch::Tensor table, torch::Tensor ids,
 
 // Hyper-parameters of one sparse apply (row or bag mode).
 SparseHp sparse_hp(long step, double lr, double beta1, double beta2,
-                   double eps, double weight_decay, double grad_scale) {
+                   double eps, double weight_decay, double grad_scale,
+                   double l1, double l2, double acc0) {
   SparseHp hp;
   hp.lr = (float)lr;
   hp.gscale = (float)grad_scale;
@@ -82,6 +83,9 @@ SparseHp sparse_hp(long step, double lr, double beta1, double beta2,
   hp.omb2 = (float)(1.0 - beta2);
   hp.bc1 = (float)(1.0 - std::pow(beta1, (double)step));
   hp.bc2 = (float)(1.0 - std::pow(beta2, (double)step));
+  hp.l1 = (float)l1;
+  hp.l2 = (float)l2;
+  hp.acc0 = (float)acc0;
   return hp;
 }
 
@@ -147,14 +151,15 @@ void sparse_apply_any(const char* op, torch::Tensor& table,
                       const torch::Tensor& grads, torch::Tensor& state1,
                       torch::Tensor& state2, torch::Tensor& shadow, long opt,
                       long step, double lr, double beta1, double beta2,
-                      double eps, double weight_decay, double grad_scale) {
+                      double eps, double weight_decay, double grad_scale,
+                      double l1, double l2, double acc0) {
   const bool bag = offsets != nullptr;
   TORCH_CHECK(table.is_cuda() && table.dim() == 2 && table.is_contiguous() &&
               table.scalar_type() == torch::kFloat32,
               op, ": table must be contiguous fp32 [V,D] on GPU");
   TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == torch::kInt64 &&
               ids.dim() == 1, op, ": ids must be i64 [n] on GPU");
-  TORCH_CHECK(opt >= SPARSE_SGD && opt <= SPARSE_ADAM,
+  TORCH_CHECK(opt >= SPARSE_SGD && opt <= SPARSE_FTRL,
               op, ": unknown optimizer code ", opt);
   const float* w = bag ? bag_args(op, ids, *offsets, *weights) : nullptr;
   const long n = ids.numel(), V = table.size(0);
@@ -174,6 +179,10 @@ void sparse_apply_any(const char* op, torch::Tensor& table,
               op, ": optimizer state tensor missing");
   TORCH_CHECK(opt != SPARSE_ADAM || (s2 != nullptr && step >= 1),
               op, ": adam needs exp_avg_sq and step >= 1");
+  TORCH_CHECK(opt != SPARSE_FTRL ||
+              (s2 != nullptr && lr > 0 && l1 >= 0 && l2 >= 0 && acc0 > 0),
+              op, ": ftrl_proximal needs the linear state and lr > 0, "
+              "l1 >= 0, l2 >= 0, initial_accumulator_value > 0");
   if (n == 0 || B == 0 || D == 0) return;   // zero-size grid: launch error
   bool gb;
   const void* g = grad_ptr(grads, &gb);
@@ -187,7 +196,7 @@ void sparse_apply_any(const char* op, torch::Tensor& table,
   const auto [sorted, perm] = stable_sort_ids(ids);
   const auto [scratch, scratch_p] = run_scratch(n, D, table.options());
   const SparseHp hp = sparse_hp(step, lr, beta1, beta2, eps, weight_decay,
-                                grad_scale);
+                                grad_scale, l1, l2, acc0);
   if (bag)
     launch_sparse_apply_bag((int)opt, table.data_ptr<float>(),
                             sorted.data_ptr<long>(), perm.data_ptr<long>(), g,
@@ -203,10 +212,10 @@ void sparse_apply(torch::Tensor table, torch::Tensor ids, torch::Tensor grads,
                   torch::Tensor state1, torch::Tensor state2,
                   torch::Tensor shadow, long opt, long step, double lr,
                   double beta1, double beta2, double eps, double weight_decay,
-                  double grad_scale) {
+                  double grad_scale, double l1, double l2, double acc0) {
   sparse_apply_any("sparse_apply", table, ids, nullptr, nullptr, false, grads,
                    state1, state2, shadow, opt, step, lr, beta1, beta2, eps,
-                   weight_decay, grad_scale);
+                   weight_decay, grad_scale, l1, l2, acc0);
 }
 
 void sparse_apply_bag(torch::Tensor table, torch::Tensor ids,
@@ -215,10 +224,10 @@ void sparse_apply_bag(torch::Tensor table, torch::Tensor ids,
                       torch::Tensor state2, torch::Tensor shadow, long opt,
                       long step, bool mean, double lr, double beta1,
                       double beta2, double eps, double weight_decay,
-                      double grad_scale) {
+                      double grad_scale, double l1, double l2, double acc0) {
   sparse_apply_any("sparse_apply_bag", table, ids, &offsets, &weights, mean,
                    grads, state1, state2, shadow, opt, step, lr, beta1, beta2,
-                   eps, weight_decay, grad_scale);
+                   eps, weight_decay, grad_scale, l1, l2, acc0);
 }
 
 // Stable partition of ids by owning shard (partition.hip): count kernel,
@@ -749,12 +758,14 @@ void bind_sparse(pybind11::module_& m) {
   m.def("embedding_gather", &embedding_gather);
   m.def("embedding_scatter_add", &embedding_scatter_add);
   m.def("sparse_apply", &sparse_apply,
-        "fused sparse SGD/momentum/Adagrad/Adam apply + bf16 shadow",
+        "fused sparse SGD/momentum/Adagrad/Adam/FTRL-Proximal apply + bf16 "
+        "shadow",
         py::arg("table"), py::arg("ids"), py::arg("grads"),
         py::arg("state1"), py::arg("state2"), py::arg("bf16_out"),
         py::arg("opt"), py::arg("step"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
-        py::arg("grad_scale"));
+        py::arg("grad_scale"), py::arg("l1") = 0.0, py::arg("l2") = 0.0,
+        py::arg("initial_accumulator_value") = 0.1);
   m.def("embedding_bag", &embedding_bag,
         "pooled (bag) embedding pull: sum / mean, optional weights",
         py::arg("table"), py::arg("ids"), py::arg("offsets"),
@@ -766,7 +777,8 @@ void bind_sparse(pybind11::module_& m) {
         py::arg("state2"), py::arg("bf16_out"), py::arg("opt"),
         py::arg("step"), py::arg("mean"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
-        py::arg("grad_scale"));
+        py::arg("grad_scale"), py::arg("l1") = 0.0, py::arg("l2") = 0.0,
+        py::arg("initial_accumulator_value") = 0.1);
   m.def("shard_partition", &shard_partition,
         "stable partition of ids by owning shard: local, perm, inv, starts",
         py::arg("ids"), py::arg("rows"), py::arg("num_shards"),

@@ -10,6 +10,7 @@ enum SparseOpt {
   SPARSE_SGD_MOM = 1,   // state1 = momentum buffer, beta1 = momentum
   SPARSE_ADAGRAD = 2,   // state1 = accumulator
   SPARSE_ADAM = 3,      // state1 = exp_avg, state2 = exp_avg_sq
+  SPARSE_FTRL = 4,      // state1 = accumulator, state2 = linear (ftrl.h)
 };
 
 struct SparseHp {
@@ -17,6 +18,7 @@ struct SparseHp {
   float beta1, beta2, eps;
   float omb1, omb2;     // 1-beta1, 1-beta2, rounded once from double
   float bc1, bc2;       // Adam bias corrections (from step)
+  float l1, l2, acc0;   // FTRL-Proximal (acc0: initial_accumulator_value)
 };
 
 // scratch: fp32 [run_scratch_rows(n), D] (run_sum.h), null when 0 rows.

@@ -39,6 +39,7 @@
 #include "common.h"
 
 #include "bag.h"
+#include "ftrl.h"
 #include "run_sum.h"
 #include "sparse_apply.h"
 
@@ -133,10 +134,15 @@ DEVINL void sum_run(const long* __restrict__ sorted,
 // One element of the optimizer step: the formulas of apply.hip's dense
 // kernels, on the row's summed gradient g. (Adam's 1-beta and bias
 // corrections arrive rounded from double: a hot row's summed gradient
-// is large enough to show fp32's error in 1.f - 0.999f.)
+// is large enough to show fp32's error in 1.f - 0.999f.) FTRL-Proximal is
+// the rule of ftrl.h (a = accumulator, c = linear term; no weight decay).
 template <int OPT>
 DEVINL void apply_elem(float& pv, float& a, float& c, float g,
                        const SparseHp& hp) {
+  if (OPT == SPARSE_FTRL) {
+    ftrl_elem(pv, a, c, g, FtrlHp{hp.lr, hp.l1, hp.l2, hp.acc0, hp.gscale});
+    return;
+  }
   float gv = g * hp.gscale;
   if (hp.wd != 0.f) gv += hp.wd * pv;
   if (OPT == SPARSE_SGD) {
@@ -238,7 +244,7 @@ __global__ __launch_bounds__(WAVES * WAVE) void sparse_apply_kernel(
       if (active) {
         ld_vec<float, VEC>(table + off, p);
         if (OPT >= SPARSE_SGD_MOM) ld_vec<float, VEC>(s1 + off, a);
-        if (OPT == SPARSE_ADAM) ld_vec<float, VEC>(s2 + off, c);
+        if (OPT >= SPARSE_ADAM) ld_vec<float, VEC>(s2 + off, c);
       }
       float g[VEC];
 #pragma unroll
@@ -264,7 +270,7 @@ __global__ __launch_bounds__(WAVES * WAVE) void sparse_apply_kernel(
           apply_elem<OPT>(p[e], a[e], c[e], g[e], hp);
         st_vec<float, VEC>(table + off, p);
         if (OPT >= SPARSE_SGD_MOM) st_vec<float, VEC>(s1 + off, a);
-        if (OPT == SPARSE_ADAM) st_vec<float, VEC>(s2 + off, c);
+        if (OPT >= SPARSE_ADAM) st_vec<float, VEC>(s2 + off, c);
         if (shadow != nullptr) st_vec<bf16_t, VEC>(shadow + off, p);
       }
     }
@@ -311,7 +317,9 @@ void launch_typed(int opt, float* table, const long* sorted, const long* perm,
     case SPARSE_SGD: DISP(SPARSE_SGD); break;
     case SPARSE_SGD_MOM: DISP(SPARSE_SGD_MOM); break;
     case SPARSE_ADAGRAD: DISP(SPARSE_ADAGRAD); break;
-    default: DISP(SPARSE_ADAM); break;
+    case SPARSE_ADAM: DISP(SPARSE_ADAM); break;
+    case SPARSE_FTRL: DISP(SPARSE_FTRL); break;
+    default: break;   // no such code: the binding has rejected it
   }
 #undef DISP
 }

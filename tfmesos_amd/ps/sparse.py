@@ -24,8 +24,8 @@ minibatch touches and push sparse row gradients back:
   scatter-adding ``-lr * grad`` into the fp32 master with the HIP
   scatter-add kernel (duplicate ids accumulate, matching TF's
   sparse-apply semantics) and refreshes the touched bf16 shadow rows.
-  Tables built with momentum, Adagrad or Adam (or ``fused_apply=True``)
-  instead sum each row's duplicates and run one optimizer step per
+  Tables built with momentum, Adagrad, Adam or FTRL-Proximal (or
+  ``fused_apply=True``) instead sum each row's duplicates and run one optimizer step per
   touched row in the fused HIP sparse-apply pass
   (``csrc/sparse_apply.hip``): master, state and shadow in one kernel,
   no float atomics, no host sync.
@@ -125,9 +125,12 @@ class _SparseOptimizer(object):
         "adagrad": {"eps": 1e-10, "weight_decay": 0.0},
         "adam": {"beta1": 0.9, "beta2": 0.999, "eps": 1e-8,
                  "weight_decay": 0.0},
+        "ftrl_proximal": {"l1": 0.0, "l2": 0.0,
+                          "initial_accumulator_value": 0.1},
     }
     _STATE = {"sgd": (), "adagrad": ("accum",),
-              "adam": ("exp_avg", "exp_avg_sq")}
+              "adam": ("exp_avg", "exp_avg_sq"),
+              "ftrl_proximal": ("accum", "linear")}
 
     def _init_optimizer(self, optimizer, hparams):
         """Validates; sets optimizer, hparams and step = 0. Returns the
@@ -163,6 +166,12 @@ class _SparseOptimizer(object):
                                eps=hp["eps"],
                                weight_decay=hp["weight_decay"],
                                bf16_out=self.shadow, **bag)
+        elif self.optimizer == "ftrl_proximal":
+            ops.sparse_ftrl(self.master, ids, grads, st["accum"],
+                            st["linear"], lr, l1=hp["l1"], l2=hp["l2"],
+                            initial_accumulator_value=hp[
+                                "initial_accumulator_value"],
+                            bf16_out=self.shadow, **bag)
         else:
             ops.sparse_adam(self.master, ids, grads, st["exp_avg"],
                             st["exp_avg_sq"], self.step, lr,
@@ -185,10 +194,17 @@ class EmbeddingTable(_SparseOptimizer):
     optimizer state rows).
 
     optimizer: "sgd" (hparams momentum, weight_decay), "adagrad" (eps,
-    weight_decay) or "adam" (beta1, beta2, eps, weight_decay; lazy — only
+    weight_decay), "adam" (beta1, beta2, eps, weight_decay; lazy — only
     touched rows and their moments move; ``step`` advances once per
-    push). Duplicate ids of one push are summed and the update runs once
-    per touched row (TF sparse-apply semantics).
+    push) or "ftrl_proximal" (l1, l2, initial_accumulator_value; no
+    weight_decay, l2 is the regulariser): FTRL-Proximal, TF's
+    FtrlOptimizer at lr_power -0.5, whose l1 term leaves weights at exactly
+    0.0. Its state rows "accum" and "linear" start at zero, and the first
+    update of an element seeds its linear term from the current weight
+    (``ops.fused_ftrl``), so a table's initial rows are trained from, not
+    thrown away — which is why it is not called "ftrl". Duplicate ids of
+    one push are summed and the update runs once per touched row (TF
+    sparse-apply semantics).
 
     Plain SGD keeps the scatter-add push unless ``fused_apply=True``
     opts it into the fused sparse-apply kernel; every other

@@ -9,7 +9,8 @@ Replaces the reference's TF variable ops on ps tasks (placed by
 * a matching flat bf16 shadow is refreshed by the SAME fused apply
   kernel that does the optimizer update — one kernel per step for the
   whole model, no per-tensor launch storm;
-* optimizer state (momentum/Adam moments/Adagrad accums) is flat too.
+* optimizer state (momentum/Adam moments/Adagrad accums/FTRL-Proximal
+  accumulator and linear term) is flat too.
 """
 
 import threading
@@ -80,6 +81,12 @@ class PStore(object):
             elif optimizer == "adagrad":
                 init_acc = self.hparams.get("initial_accumulator", 0.1)
                 self.state["accum"] = torch.full_like(self.flat, init_acc)
+            elif optimizer == "ftrl_proximal":
+                # hparams lr, l1, l2, initial_accumulator_value; the state
+                # starts at zero (ops.fused_ftrl adds the initial
+                # accumulator value on read)
+                self.state["accum"] = torch.zeros_like(self.flat)
+                self.state["linear"] = torch.zeros_like(self.flat)
             self.global_step = 0
 
     def view(self, name, bf16=False):
@@ -154,6 +161,12 @@ class PStore(object):
                                   lr, eps=hp.get("eps", 1e-10),
                                   weight_decay=hp.get("weight_decay", 0.0),
                                   bf16_out=bf, grad_scale=grad_scale)
+            elif self.opt == "ftrl_proximal":
+                ops.fused_ftrl(p, g, st["accum"], st["linear"], lr,
+                               l1=hp.get("l1", 0.0), l2=hp.get("l2", 0.0),
+                               initial_accumulator_value=hp.get(
+                                   "initial_accumulator_value", 0.1),
+                               bf16_out=bf, grad_scale=grad_scale)
             else:
                 raise ValueError("unknown optimizer %r" % self.opt)
 

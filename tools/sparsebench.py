@@ -9,7 +9,9 @@ pushed rows of bf16 grads, two id sets:
 
 Versions: plain SGD through the scatter-add path (fused_apply=False —
 fp32 atomics + unique + shadow refresh) against the fused sparse-apply
-kernel (fused_apply=True), plus Adagrad and Adam (fused kernel only).
+kernel (fused_apply=True), plus Adagrad, Adam and FTRL-Proximal (fused
+kernel only; FTRL-Proximal moves Adam's bytes, so the Adam row is its
+yardstick and the ratio is printed).
 
 Method: device events; every (version, id set) is warmed up; each timing
 window lasts at least --window seconds; the versions alternate inside
@@ -36,6 +38,7 @@ VERSIONS = [
     ("sgd fused       (fused_apply=True)", "sgd", {"fused_apply": True}),
     ("adagrad fused", "adagrad", {}),
     ("adam fused", "adam", {}),
+    ("ftrl_proximal fused", "ftrl_proximal", {"l1": 0.001, "l2": 0.001}),
 ]
 
 
@@ -104,6 +107,7 @@ def main():
                                                 "min-max ms")]
     tables = [(label, big_table(V, D, dev, opt, hp))
               for label, opt, hp in VERSIONS]
+    median = {}
     for idname, ids in idsets:
         for _, t in tables:            # warm every (version, id set)
             for _ in range(3):
@@ -118,12 +122,17 @@ def main():
                 iters[label] = it
         for label, t in tables:
             ts = sorted(times[label])
-            s = ts[len(ts) // 2]
+            s = median[(label, idname)] = ts[len(ts) // 2]
             nbytes = n * (8 + 2 * D) + touched[idname] * D * (
                 4 + 4 + 2 + 8 * len(t.state))
             lines.append("%-38s %-8s %10.3f %10.1f %7d   %.3f-%.3f"
                          % (label, idname, s * 1e3, nbytes / s / 1e9,
                             iters[label], ts[0] * 1e3, ts[-1] * 1e3))
+    for idname, _ in idsets:
+        f = median[("ftrl_proximal fused", idname)]
+        a = median[("adam fused", idname)]
+        lines.append("ftrl_proximal / adam (%s): %.3f ms / %.3f ms = %.3f"
+                     % (idname, f * 1e3, a * 1e3, f / a))
     # same result? one push of each SGD version from identical state, at
     # the timed size (the atomics' arrival order may move last bits)
     del tables
