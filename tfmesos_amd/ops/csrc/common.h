@@ -37,11 +37,23 @@ struct SmallSgdArgs {
 // two small bf16 ranges into dst[0..n0) and dst[off1..off1+n1) — the
 // mnist step snapshots the classifier shadow there, one launch ahead
 // of the fused head+tail kernel that reads it
+// rows > 0: s0 is a [rows, cols] classifier (rows <= 128, cols <= 16)
+// and the job also lays out, zero-padded and whole on every call, the
+// two operand images the fused kernel's waves would otherwise each build
+// from it: the k-major [16][136] logits operand at dst[kSnapKmajOff..)
+// and the [128][16] row image at dst[kSnapRowOff..).
 struct SnapArgs {
   const void* s0; const void* s1;
   void* dst;
   int n0, n1, off1;
+  int rows, cols;
 };
+
+// the mnist snapshot buffer, in bf16 elements
+constexpr int kSnapB2Off = 2048;
+constexpr int kSnapKmajOff = kSnapB2Off + 64;
+constexpr int kSnapRowOff = kSnapKmajOff + 16 * 136;
+constexpr int kSnapElems = kSnapRowOff + 128 * 16;
 
 // host-side descriptor for the fused head+tail kernel (gemm.hip)
 struct HeadTailArgs {

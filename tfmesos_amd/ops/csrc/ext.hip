@@ -372,10 +372,10 @@ torch::Tensor gemm_bias_act_route(torch::Tensor a, torch::Tensor b,
 // one-launch forward, or the small stripe reduce) also snapshots the
 // classifier shadow (w2s [H,C], b2s [C]) for the fused head+tail kernel
 // that follows. Returns (h, snap): snap is the per-device snapshot
-// buffer (w2 at 0, b2 at 2048), or EMPTY when the GEMM took a kernel
-// path that takes no snapshot — the caller then uses the live shadow
-// and the arrival ticket.
-constexpr int kSnapB2Off = 2048;
+// buffer (w2 at 0, b2 at 2048, then the two zero-padded operand images
+// of SnapArgs), or EMPTY when the GEMM took a kernel path that takes no
+// snapshot — the caller then uses the live shadow and the arrival
+// ticket.
 std::vector<torch::Tensor> mlp_fwd_snap(torch::Tensor x, torch::Tensor w1,
                                         torch::Tensor b1, torch::Tensor w2s,
                                         torch::Tensor b2s) {
@@ -383,15 +383,17 @@ std::vector<torch::Tensor> mlp_fwd_snap(torch::Tensor x, torch::Tensor w1,
     TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
                 t->scalar_type() == torch::kBFloat16,
                 "w2s/b2s must be contiguous bf16 on GPU");
-  TORCH_CHECK(w2s.numel() <= kSnapB2Off && b2s.numel() <= 16,
+  TORCH_CHECK(w2s.dim() == 2 && w2s.size(0) <= 128 && w2s.size(1) <= 16 &&
+              w2s.size(1) >= 1 && b2s.numel() <= 16,
               "classifier too large for the snapshot buffer");
   static std::unordered_map<int, torch::Tensor> smap;
   auto& sb = smap[x.device().index()];
   if (!sb.defined())
-    sb = torch::zeros({kSnapB2Off + 64}, w2s.options());
+    sb = torch::zeros({kSnapElems}, w2s.options());
   SnapArgs sa;
   sa.s0 = w2s.data_ptr(); sa.s1 = b2s.data_ptr(); sa.dst = sb.data_ptr();
   sa.n0 = (int)w2s.numel(); sa.n1 = (int)b2s.numel(); sa.off1 = kSnapB2Off;
+  sa.rows = (int)w2s.size(0); sa.cols = (int)w2s.size(1);
   bool taken = false;
   auto empty = torch::empty({0}, x.options());
   auto h = gemm_bias_act_impl(x, w1, b1, 1, false, false, empty, empty,
@@ -1422,8 +1424,8 @@ torch::Tensor mlp_head_tail_sgd(torch::Tensor x, torch::Tensor h,
     // W2/b2 as mlp_fwd_snap's launch copied them: no ticket needed
     TORCH_CHECK(snap.is_cuda() && snap.is_contiguous() &&
                 snap.scalar_type() == torch::kBFloat16 &&
-                snap.numel() >= kSnapB2Off + 16 &&
-                w2s.numel() <= kSnapB2Off,
+                snap.numel() >= kSnapElems &&
+                (uintptr_t)snap.data_ptr() % 16 == 0,
                 "snap must be mlp_fwd_snap's buffer");
     hta.w2 = snap.data_ptr();
     hta.b2 = (const bf16_t*)snap.data_ptr() + kSnapB2Off;

@@ -326,6 +326,27 @@ void gemm_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B,
   }
 }
 
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+// Range-checked loads: a raw buffer descriptor over a wave-uniform base
+// and the byte extent of the tensor VIEW that was passed. A lane whose
+// offset lies beyond the extent receives zeros from the hardware — no
+// clamped address, no 64-bit add, no select after the load and no
+// predicate kept alive across the loads. Offsets are 32-bit bytes; a
+// predicate that is constant per lane is folded into the lane's base
+// offset once (BUF_OOB: beyond every extent, with room to add to).
+typedef __amdgpu_buffer_rsrc_t brsrc_t;
+constexpr int BUF_OOB = 0x40000000;
+
+DEVINL brsrc_t buf_rsrc(const void* p, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes,
+                                           0x00020000);
+}
+DEVINL float buf_f32(brsrc_t r, int off) {
+  return __builtin_bit_cast(float,
+                            __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
+}
+
 // split-K phase 2: out[i] = act(sum_z ws[z][i] + bias), f32x4-vectorized
 // over the flattened [M,ldc] output (ldc == N, contiguous).
 // 1-elem/thread variant for SMALL outputs (mnist fwd: mn = 10k gave
@@ -337,7 +358,76 @@ struct SnapJob {
   const __bf16* s0; const __bf16* s1;
   __bf16* dst;
   int n0, n1, off1;
+  int rows, cols;   // > 0: s0 is [rows, cols], the images are laid out too
 };
+
+// The two operand images of a [rows, cols] classifier that
+// mlp_head_tail_kernel's waves consume (see SnapArgs), as b128 chunks in
+// wave-sized groups g < SNAP_NG: groups 0-3 are the 128 live k of the
+// k-major [CP][HP] image (chunk = eight k of one class row), groups 4-7
+// the [HB][CP] row image (chunk = half a row) and group 8 the k-major
+// image's 16 pad chunks. Zero beyond rows and cols, so every chunk of
+// both images is written on every snapshot and nothing of an earlier
+// classifier survives. One block pays the (row, class) arithmetic here;
+// every wave of the consumer then moves whole chunks.
+// g is wave-uniform, so a wave runs one of the three forms. The loads
+// are range-checked (buf_rsrc): a row >= rows is beyond the extent
+// whatever the class, the class predicate is folded into the offset.
+constexpr int SNAP_NG = 9;
+static_assert(kSnapRowOff - kSnapKmajOff == CP * HP &&
+              kSnapElems - kSnapRowOff == HB * CP && HP == HB + 8 &&
+              HB * CP / 8 == 4 * WAVE, "snapshot layout");
+
+struct SnapChunk {
+  unsigned e[8];   // one element per register: packed only when stored,
+};                 // so the loads can stay in flight meanwhile
+
+DEVINL SnapChunk snap_chunk_load(const SnapJob& sj, int g, int lane) {
+  const brsrc_t r = buf_rsrc(sj.s0, sj.rows * sj.cols * 2);
+  const int q = (g & 3) * WAVE + lane;
+  int off[8];
+  if (g < 4) {          // class q >> 4, rows (q & 15) * 8 + j
+    const int c = q >> 4;
+    const int base =
+        c < sj.cols ? ((q & 15) * 8 * sj.cols + c) * 2 : BUF_OOB;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) off[j] = base + j * sj.cols * 2;
+  } else {              // row q >> 1, classes (q & 1) * 8 + j
+    const int c0 = (q & 1) * 8;
+    const int base = ((q >> 1) * sj.cols + c0) * 2;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      off[j] = (g < 8 && c0 + j < sj.cols) ? base + j * 2 : BUF_OOB;
+  }
+  SnapChunk ch;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    ch.e[j] = __builtin_amdgcn_raw_buffer_load_b16(r, off[j], 0, 0);
+  return ch;
+}
+
+DEVINL void snap_chunk_store(const SnapJob& sj, int g, int lane,
+                             const SnapChunk& ch) {
+  // the empty asm pins the packing here: the compiler otherwise moves the
+  // shifts up to the loads, and with them the wait for the loads
+  unsigned e[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    e[j] = ch.e[j];
+    asm volatile("" : "+v"(e[j]));
+  }
+  u32x4 d;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) d[j] = e[2 * j] | (e[2 * j + 1] << 16);
+  const bf16x8 v = __builtin_bit_cast(bf16x8, d);
+  const int q = (g & 3) * WAVE + lane;
+  if (g < 4)
+    *(bf16x8*)&sj.dst[kSnapKmajOff + (q >> 4) * HP + (q & 15) * 8] = v;
+  else if (g < 8)
+    *(bf16x8*)&sj.dst[kSnapRowOff + q * 8] = v;
+  else if (lane < CP)
+    *(bf16x8*)&sj.dst[kSnapKmajOff + lane * HP + HB] = v;
+}
 
 template <int ACT, bool BIAS, bool OUTF32>
 __global__ __launch_bounds__(256)
@@ -349,6 +439,12 @@ void splitk_reduce_small_kernel(const float* __restrict__ ws,
     for (int j = threadIdx.x; j < sj.n0; j += 256) sj.dst[j] = sj.s0[j];
     for (int j = threadIdx.x; j < sj.n1; j += 256)
       sj.dst[sj.off1 + j] = sj.s1[j];
+    if (sj.rows > 0) {
+      const int lane = threadIdx.x & 63;
+      for (int g = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+           g < SNAP_NG; g += 4)
+        snap_chunk_store(sj, g, lane, snap_chunk_load(sj, g, lane));
+    }
   }
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= mn) return;
@@ -458,7 +554,6 @@ void splitk_reduce_kernel(const float* __restrict__ ws, const void* __restrict__
 // by the last (ragged) block; its loads are issued first and stored before
 // the barrier, so the copy rides under the GEMM's own round trip.
 typedef bf16x8 __attribute__((aligned(4))) bf16x8_a4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int F1_KS = 3;   // k-steps in flight per wave
 // shipped tile (launch_gemm_fwd1's variant code); measurements of all
@@ -515,13 +610,20 @@ void gemm_fwd1_kernel(const __bf16* __restrict__ A,
   const bool snapper = sj.dst != nullptr && blockIdx.x == gridDim.x - 1 &&
                        blockIdx.y == gridDim.y - 1;
   const int sn = sj.n0 + sj.n1;
+  const bool imgs = sj.rows > 0;
+  const int zu = __builtin_amdgcn_readfirstlane(z);   // provably uniform
   __bf16 sv[2] = {};
-  if (snapper) {
+  SnapChunk sc = {};
+  // unlikely: one block per launch — its code goes behind the kernel's
+  // end instead of standing between every block's prologue and k loop
+  if (__builtin_expect(snapper, 0)) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int j = t + u * nth;
       if (j < sn) sv[u] = j < sj.n0 ? sj.s0[j] : sj.s1[j - sj.n0];
     }
+    // this wave's first group of image chunks
+    if (imgs && zu < SNAP_NG) sc = snap_chunk_load(sj, zu, lane);
   }
 
   // this thread's first epilogue element (see the combine loop): its
@@ -622,7 +724,7 @@ void gemm_fwd1_kernel(const __bf16* __restrict__ A,
       *(bf16x8*)&img[((fm * FN + fn) * 64 + lane) * 8] =
           __builtin_bit_cast(bf16x8, acc[fm][fn]);
 
-  if (snapper) {
+  if (__builtin_expect(snapper, 0)) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int j = t + u * nth;
@@ -631,6 +733,11 @@ void gemm_fwd1_kernel(const __bf16* __restrict__ A,
     for (int j = t + 2 * nth; j < sn; j += nth)
       sj.dst[j < sj.n0 ? j : sj.off1 + (j - sj.n0)] =
           j < sj.n0 ? sj.s0[j] : sj.s1[j - sj.n0];
+    if (imgs) {
+      if (zu < SNAP_NG) snap_chunk_store(sj, zu, lane, sc);
+      for (int g = zu + nslice; g < SNAP_NG; g += nslice)
+        snap_chunk_store(sj, g, lane, snap_chunk_load(sj, g, lane));
+    }
   }
   __syncthreads();
 
@@ -776,6 +883,22 @@ DEVINL void small_sgd_fetch(const SmallSgd& sg, SmallSgdPre& pre, bool cs,
     const int nn = n0 + (lane & 31);
     pre.b = sg.pmb[nn < N ? nn : 0];
   }
+}
+
+// small_sgd_fetch for the fused head+tail kernel (ldc == N): the same
+// elements, range-checked instead of clamped. Row m >= M lies beyond
+// the extent together with every column n < N.
+DEVINL void small_sgd_fetch_buf(const SmallSgd& sg, SmallSgdPre& pre, int m0,
+                                int n0, int M, int N, int w, int lane) {
+  const brsrc_t wr = buf_rsrc(sg.pmw, M * N * 4);
+  const int n = n0 + (lane & 31);
+  const int nb = n < N ? n * 4 : BUF_OOB;
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    pre.w[u] = buf_f32(wr, nb + small_sgd_row(m0, w, u, lane) * N * 4);
+  pre.b = 0.f;
+  if (blockIdx.x == 0 && sg.pmb != nullptr)
+    pre.b = buf_f32(buf_rsrc(sg.pmb, N * 4), n * 4);
 }
 
 DEVINL void small_sgd_commit(const SmallSgd& sg, const SmallSgdPre& pre,
@@ -1177,12 +1300,16 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
   // half), this wave's 32 rows of h (b64 chunks, two rows per pass), the
   // classifier (one hidden row per lane), its bias, the labels and —
   // APPLY — the fp32 masters this lane updates after the barrier.
-  // All of them are unconditional loads from addresses clamped into
-  // the tensor (element 0 where the lane has nothing to read) with the
-  // select and every conversion AFTER the last load: a load guarded by
-  // a lane condition gets a branch of its own, and the compiler drains
-  // the loads in flight (s_waitcnt vmcnt(0)) inside such branches —
-  // the guarded form of this prologue was three round trips, not one.
+  // All of them are unconditional, range-checked buffer loads (see
+  // buf_rsrc: a lane with nothing to read sits beyond the extent and
+  // gets zeros) with every conversion AFTER the last load: a load
+  // guarded by a lane condition gets a branch of its own, and the
+  // compiler drains the loads in flight (s_waitcnt vmcnt(0)) inside
+  // such branches — the guarded form of this prologue was three round
+  // trips, not one. In x, h and the masters a row beyond the tensor is
+  // beyond the extent whatever the column, so only the column
+  // predicate, constant per lane, is folded into the offset. (The
+  // !SNAP classifier gather keeps clamped addresses and selects.)
   const int gk = ks + kk;
   const int gm = m0 + half * 16;
   const bool xvec = (M & 7) == 0;       // rows of x are whole b128 chunks
@@ -1194,37 +1321,60 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
   // the compiler must assume pending on them.
   unsigned xs[16];
   {
-    const __bf16* rowp = X + (long)(gk < ke ? gk : 0) * M;
+    const brsrc_t xr = buf_rsrc(X, K * M * 2);
+    const int xrow = gk * M + gm;
     if (xvec) {
       // M % 8 == 0 and gm % 8 == 0: a chunk is whole or absent
-      ra0 = *(const bf16x8*)(rowp + (gm < M ? gm : 0));
-      ra1 = *(const bf16x8*)(rowp + (gm + 8 < M ? gm + 8 : 0));
+      ra0 = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+          xr, gm < M ? xrow * 2 : BUF_OOB, 0, 0));
+      ra1 = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+          xr, gm + 8 < M ? (xrow + 8) * 2 : BUF_OOB, 0, 0));
     } else {
 #pragma unroll
       for (int j = 0; j < 16; ++j)
-        xs[j] = ((const unsigned short*)rowp)[gm + j < M ? gm + j : 0];
+        xs[j] = __builtin_amdgcn_raw_buffer_load_b16(
+            xr, gm + j < M ? (xrow + j) * 2 : BUF_OOB, 0, 0);
     }
   }
   const int hc4 = kk * 4;               // this lane's h columns
   bf16x4 hv[16];
+  {
+    const brsrc_t hr = buf_rsrc(ht.h, K * N * 2);
+    const int hb = (hc4 < N ? hc4 * 2 : BUF_OOB) + (ks + half) * N * 2;
 #pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int r = ks + 2 * i + half;
-    const long off = (r < K && hc4 < N) ? (long)r * N + hc4 : 0;
-    hv[i] = *(const bf16x4*)&ht.h[off];
+    for (int i = 0; i < 16; ++i)
+      hv[i] = __builtin_bit_cast(bf16x4, __builtin_amdgcn_raw_buffer_load_b64(
+          hr, hb + 2 * i * N * 2, 0, 0));
   }
+  // SNAP: the snapshot's producer laid both classifier images out,
+  // zero-padded (SnapJob) — four b128 chunks of the k-major one per lane
+  // (the 128 live k of each class row; the pad columns are never read)
+  // and one chunk of this block's 32 rows of the row image
   __bf16 wv[2][CP];
+  bf16x8 wkm[4], wrow;
+  if (SNAP) {
 #pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int hr = lane + q * 64;
+    for (int j = 0; j < 4; ++j) {
+      const int q = lane + j * 64;
+      wkm[j] = *(const bf16x8*)&ht.w2[kSnapKmajOff + (q >> 4) * HP +
+                                      (q & 15) * 8];
+    }
+    wrow = *(const bf16x8*)&ht.w2[kSnapRowOff + n0 * CP + lane * 8];
+  } else {
 #pragma unroll
-    for (int c = 0; c < CP; ++c)
-      wv[q][c] = ht.w2[(hr < N && c < C) ? hr * C + c : 0];
+    for (int q = 0; q < 2; ++q) {
+      const int hr = lane + q * 64;
+#pragma unroll
+      for (int c = 0; c < CP; ++c)
+        wv[q][c] = ht.w2[(hr < N && c < C) ? hr * C + c : 0];
+    }
   }
-  const bf16_t braw = ht.b2[kk < C ? kk : 0];
+  const unsigned braw =
+      __builtin_amdgcn_raw_buffer_load_b16(buf_rsrc(ht.b2, C * 2), kk * 2, 0, 0);
   // the label's low dword is all (int)label keeps; a b64 load's unused
   // high register was reused at once, behind a vmcnt(0)
-  const int lraw = ((const int*)ht.labels)[2 * (ks + kk < K ? ks + kk : 0)];
+  const int label = (int)__builtin_amdgcn_raw_buffer_load_b32(
+      buf_rsrc(ht.labels, K * 8), (ks + kk) * 8, 0, 0);
   SmallSgdPre pre = {};
   float pm2[16] = {};
   float pm2bv = 0.f;
@@ -1232,51 +1382,39 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
   const bool snap_head =
       APPLY && SNAP && blockIdx.x == gridDim.x - 1 && blockIdx.y == 0;
   if (APPLY) {
-    small_sgd_fetch(sg, pre, true, m0, n0, M, N, N, w, lane);
+    small_sgd_fetch_buf(sg, pre, m0, n0, M, N, w, lane);
     if (snap_head) {
+      const brsrc_t w2r = buf_rsrc(sg.pm2w, N * C * 4);
+      const int cb = kk < C ? kk * 4 : BUF_OOB;
 #pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const int hrow = ks + head_frag_row(v, lane);
-        pm2[v] = sg.pm2w[(kk < C && hrow < N) ? hrow * C + kk : 0];
-      }
-      pm2bv = sg.pm2b[t < C ? t : 0];
+      for (int v = 0; v < 16; ++v)
+        pm2[v] = buf_f32(w2r, cb + (ks + head_frag_row(v, lane)) * C * 4);
+      pm2bv = buf_f32(buf_rsrc(sg.pm2b, C * 4), t * 4);
     }
   }
 
-  // 2. selects and conversions, then the LDS images (zeros beyond B, H
-  // and C, so none of them needs a separate clear pass over live data)
-  const bf16x4 z4 = {};
+  // 2. conversions, then the LDS images (zeros beyond B, H and C, so
+  // none of them needs a separate clear pass over live data)
+  if (!SNAP) {
 #pragma unroll
-  for (int i = 0; i < 16; ++i)
-    if (!(ks + 2 * i + half < K && hc4 < N)) hv[i] = z4;
+    for (int q = 0; q < 2; ++q)
 #pragma unroll
-  for (int q = 0; q < 2; ++q)
+      for (int c = 0; c < CP; ++c)
+        if (!(lane + q * 64 < N && c < C)) wv[q][c] = (__bf16)0.f;
+  }
+  const float bc = __builtin_bit_cast(float, braw << 16);   // 0 beyond C
+  if (!xvec) {
+    u32x4 d0, d1;
 #pragma unroll
-    for (int c = 0; c < CP; ++c)
-      if (!(lane + q * 64 < N && c < C)) wv[q][c] = (__bf16)0.f;
-  const float bc = kk < C ? bf2f(braw) : 0.f;
-  const int label = (lane < 32 && ks + lane < K) ? (int)lraw : 0;
-  {
-    const bf16x8 z8x = {};
-    if (xvec) {
-      if (!(gk < ke && gm < M)) ra0 = z8x;
-      if (!(gk < ke && gm + 8 < M)) ra1 = z8x;
-    } else {
-      u32x4 d0, d1;
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        if (!(gk < ke && gm + j < M)) xs[j] = 0u;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        d0[j] = xs[2 * j] | (xs[2 * j + 1] << 16);
-        d1[j] = xs[8 + 2 * j] | (xs[9 + 2 * j] << 16);
-      }
-      ra0 = __builtin_bit_cast(bf16x8, d0);
-      ra1 = __builtin_bit_cast(bf16x8, d1);
+    for (int j = 0; j < 4; ++j) {
+      d0[j] = xs[2 * j] | (xs[2 * j + 1] << 16);
+      d1[j] = xs[8 + 2 * j] | (xs[9 + 2 * j] << 16);
     }
+    ra0 = __builtin_bit_cast(bf16x8, d0);
+    ra1 = __builtin_bit_cast(bf16x8, d1);
   }
 
-  {
+  if (!SNAP) {
     const bf16x8 z8 = {};
     for (int i = lane * 8; i < CP * HP; i += 64 * 8) *(bf16x8*)&wtw[i] = z8;
     *(bf16x8*)&wpw[lane * 8] = z8;
@@ -1284,23 +1422,32 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
 #pragma unroll
   for (int i = 0; i < 16; ++i)
     *(bf16x4*)&hs[(ks + 2 * i + half) * HP + hc4] = hv[i];
-  // wtw: column hr of the [c][k] image, all CP classes (wv is zero
-  // beyond C and H — the same zeros the clear put there); wpw: the
-  // lane's whole row of the N tile as two b128 stores
+  if (SNAP) {
 #pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int hr = lane + q * 64;
+    for (int j = 0; j < 4; ++j) {
+      const int q = lane + j * 64;
+      *(bf16x8*)&wtw[(q >> 4) * HP + (q & 15) * 8] = wkm[j];
+    }
+    *(bf16x8*)&wpw[lane * 8] = wrow;
+  } else {
+    // wtw: column hr of the [c][k] image, all CP classes (wv is zero
+    // beyond C and H — the same zeros the clear put there); wpw: the
+    // lane's whole row of the N tile as two b128 stores
 #pragma unroll
-    for (int c = 0; c < CP; ++c) wtw[c * HP + hr] = wv[q][c];
-    if (hr >= n0 && hr < n0 + 32 && hr < N) {
-      bf16x8 lo, hi;
+    for (int q = 0; q < 2; ++q) {
+      const int hr = lane + q * 64;
 #pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        lo[c] = wv[q][c];
-        hi[c] = wv[q][8 + c];
+      for (int c = 0; c < CP; ++c) wtw[c * HP + hr] = wv[q][c];
+      if (hr >= n0 && hr < n0 + 32 && hr < N) {
+        bf16x8 lo, hi;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          lo[c] = wv[q][c];
+          hi[c] = wv[q][8 + c];
+        }
+        *(bf16x8*)&wpw[(hr - n0) * CP] = lo;
+        *(bf16x8*)&wpw[(hr - n0) * CP + 8] = hi;
       }
-      *(bf16x8*)&wpw[(hr - n0) * CP] = lo;
-      *(bf16x8*)&wpw[(hr - n0) * CP + 8] = hi;
     }
   }
 
@@ -1677,6 +1824,7 @@ void launch_gemm(const bf16_t* A, const bf16_t* B, const void* bias,
       sj.s0 = (const __bf16*)snap->s0; sj.s1 = (const __bf16*)snap->s1;
       sj.dst = (__bf16*)snap->dst;
       sj.n0 = snap->n0; sj.n1 = snap->n1; sj.off1 = snap->off1;
+      sj.rows = snap->rows; sj.cols = snap->cols;
       if (snap_taken) *snap_taken = true;
     }
 #define RLAUNCH(ACTv, BIASv, OUTv)                                          \
@@ -1735,6 +1883,7 @@ void launch_gemm_fwd1(const bf16_t* A, const bf16_t* B, const void* bias,
     sj.s0 = (const __bf16*)snap->s0; sj.s1 = (const __bf16*)snap->s1;
     sj.dst = (__bf16*)snap->dst;
     sj.n0 = snap->n0; sj.n1 = snap->n1; sj.off1 = snap->off1;
+    sj.rows = snap->rows; sj.cols = snap->cols;
   }
   if (snap_taken) *snap_taken = snap != nullptr;
   if (variant < 0) variant = kFwd1Tile;
