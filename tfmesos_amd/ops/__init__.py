@@ -1861,13 +1861,18 @@ class _BatchNormActFn(torch.autograd.Function):
 
 
 class _GroupBNFn(torch.autograd.Function):
-    """Grouped train-mode BN(+relu) over the terminal branches of an
+    """Grouped train-mode BN(+relu) over parallel branches of an
     Inception block: ONE stats/finalize/apply launch triple for ALL
     branches (per-channel math — results identical to per-branch BNs;
     at these layer sizes the per-kernel execution floor made launch
-    count the dominant BN cost). Writes into a channel-narrow view of
-    the block's concat buffer and returns it (same .detach() contract
-    as _BatchNormActFn's out= path; see _JoinViews)."""
+    count the dominant BN cost).
+
+    out_view None: the branches get separate dense outputs, returned as
+    a tuple (inner-stage BNs feeding different consumers). Otherwise the
+    results go into consecutive channel slices of out_view, a
+    channel-narrow view of the block's concat buffer, which is returned
+    (same .detach() contract as _BatchNormActFn's out= path; see
+    _JoinViews)."""
 
     @staticmethod
     def forward(ctx, out_view, eps, relu, n, *args):
@@ -1875,53 +1880,12 @@ class _GroupBNFn(torch.autograd.Function):
               for a in args[:n]]
         gs = [g.to(torch.bfloat16) for g in args[n:2 * n]]
         bs = [b.to(torch.bfloat16) for b in args[2 * n:3 * n]]
-        mean, invstd = _ext().bn_group_fwd(xs, gs, bs, out_view,
-                                           eps, relu)
+        outs = [] if out_view is None else [out_view]
+        *ys, mean, invstd = _ext().bn_group_fwd(xs, gs, bs, outs, eps, relu)
         ctx.save_for_backward(mean, invstd, *xs, *gs, *bs)
         ctx.n = n
         ctx.relu = relu
-        return out_view.detach()
-
-    @staticmethod
-    def backward(ctx, dy):
-        n = ctx.n
-        saved = ctx.saved_tensors
-        mean, invstd = saved[0], saved[1]
-        xs = list(saved[2:2 + n])
-        gs = list(saved[2 + n:2 + 2 * n])
-        bs = list(saved[2 + 2 * n:2 + 3 * n])
-        if not _is_cl_narrow(dy):
-            dy = dy.contiguous(memory_format=torch.channels_last)
-        outs = _ext().bn_group_bwd(xs, dy, gs, bs, mean, invstd, ctx.relu)
-        dxs = outs[:n]
-        dgamma, dbeta = outs[n], outs[n + 1]
-        dgs, dbs = [], []
-        off = 0
-        for g in gs:
-            c = g.numel()
-            dgs.append(dgamma[off:off + c])
-            dbs.append(dbeta[off:off + c])
-            off += c
-        return (None, None, None, None, *dxs, *dgs, *dbs)
-
-
-class _GroupBNMultiFn(torch.autograd.Function):
-    """Grouped BN over PARALLEL inner-stage branches with separate
-    dense outputs (e.g. the two 1x1 stems of an Inception block): one
-    stats/finalize/apply launch triple instead of one per branch."""
-
-    @staticmethod
-    def forward(ctx, eps, relu, n, *args):
-        xs = [a.contiguous(memory_format=torch.channels_last)
-              for a in args[:n]]
-        gs = [g.to(torch.bfloat16) for g in args[n:2 * n]]
-        bs = [b.to(torch.bfloat16) for b in args[2 * n:3 * n]]
-        outs = _ext().bn_group_fwd_multi(xs, gs, bs, eps, relu)
-        ys, mean, invstd = outs[:n], outs[n], outs[n + 1]
-        ctx.save_for_backward(mean, invstd, *xs, *gs, *bs)
-        ctx.n = n
-        ctx.relu = relu
-        return tuple(ys)
+        return tuple(ys) if out_view is None else out_view.detach()
 
     @staticmethod
     def backward(ctx, *dys):
@@ -1931,28 +1895,22 @@ class _GroupBNMultiFn(torch.autograd.Function):
         xs = list(saved[2:2 + n])
         gs = list(saved[2 + n:2 + 2 * n])
         bs = list(saved[2 + 2 * n:2 + 3 * n])
+        # one dy per output: per branch, or the one over the concat view
         dys = [d if _is_cl_narrow(d)
                else d.contiguous(memory_format=torch.channels_last)
                for d in dys]
-        outs = _ext().bn_group_bwd_multi(xs, dys, gs, bs, mean, invstd,
-                                         ctx.relu)
-        dxs = outs[:n]
-        dgamma, dbeta = outs[n], outs[n + 1]
-        dgs, dbs = [], []
-        off = 0
-        for g in gs:
-            c = g.numel()
-            dgs.append(dgamma[off:off + c])
-            dbs.append(dbeta[off:off + c])
-            off += c
-        return (None, None, None, *dxs, *dgs, *dbs)
+        widths = [g.numel() for g in gs]
+        *dxs, dgamma, dbeta = _ext().bn_group_bwd(
+            xs, dys, gs, bs, mean, invstd, ctx.relu)
+        return (None, None, None, None, *dxs, *dgamma.split(widths),
+                *dbeta.split(widths))
 
 
 def bn_group_multi(xs, weights, biases, eps=1e-3, relu=True):
     """Grouped BN for parallel branches with separate outputs (GPU
     only). Returns the per-branch normalized tensors."""
-    return _GroupBNMultiFn.apply(eps, relu, len(xs), *xs,
-                                 *weights, *biases)
+    return _GroupBNFn.apply(None, eps, relu, len(xs), *xs,
+                            *weights, *biases)
 
 
 def bn_group_apply(out_view, xs, weights, biases, eps=1e-3, relu=True):

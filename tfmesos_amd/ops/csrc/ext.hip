@@ -937,26 +937,59 @@ static bool cl_narrow(const torch::Tensor& t, long* ldy) {
   return true;
 }
 
+// the flat-walk kernels decode a 32-bit flat index
+static bool bn_flat_ok(long P, long C) { return P * C < (1L << 31); }
+
+static bool bn_is_vec(const torch::Tensor& t, torch::ScalarType dt, long n) {
+  return t.is_cuda() && t.is_contiguous() && t.scalar_type() == dt &&
+         t.numel() == n;
+}
+
+// x, g, b of bn_fwd / bn_bwd. The size checks come before the layout
+// check: they need only the shape. Returns the plan both directions
+// size `part` from and hand to their launcher.
+static BnPlan bn_check(const char* who, const torch::Tensor& x,
+                       const torch::Tensor& g, const torch::Tensor& b,
+                       int* C, long* P) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.numel() > 0 &&
+              x.scalar_type() == torch::kBFloat16,
+              who, ": x must be bf16 channels-last");
+  TORCH_CHECK(x.size(1) <= bn_max_channels(), who, ": C > ",
+              bn_max_channels(), " (LDS staging bound)");
+  *C = (int)x.size(1);
+  *P = x.numel() / *C;
+  const BnPlan plan = bn_plan(*P, *C);
+  TORCH_CHECK(plan.rw_apply || bn_flat_ok(*P, *C), who,
+              ": P*C >= 2^31 with C % 8 != 0 (flat-walk index bound)");
+  TORCH_CHECK(is_cl(x), who, ": x must be bf16 channels-last");
+  TORCH_CHECK(bn_is_vec(g, torch::kBFloat16, *C) &&
+              bn_is_vec(b, torch::kBFloat16, *C),
+              who, ": g/b must be bf16 [C]");
+  return plan;
+}
+
+std::tuple<std::string, std::string, long> bn_plan_py(long P, long C) {
+  TORCH_CHECK(P > 0 && C > 0 && C <= bn_max_channels(),
+              "bn_plan: bad argument");
+  const BnPlan p = bn_plan(P, (int)C);
+  return {p.rw_stats ? "rowwise" : "column", p.rw_apply ? "rowwise" : "flat",
+          p.Z};
+}
+
 std::vector<torch::Tensor> bn_fwd(torch::Tensor x, torch::Tensor g,
                                   torch::Tensor b, double eps, bool relu,
                                   torch::Tensor out) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && is_cl(x) &&
-              x.scalar_type() == torch::kBFloat16,
-              "x must be bf16 channels-last");
-  const int C = x.size(1);
-  const long P = x.numel() / C;
-  TORCH_CHECK(C <= bn_max_channels(), "bn: C > LDS staging bound");
-  TORCH_CHECK(g.numel() == C && b.numel() == C &&
-              g.scalar_type() == torch::kBFloat16 &&
-              b.scalar_type() == torch::kBFloat16, "g/b must be bf16 [C]");
-  const int Z = bn_stats_slices(P, C);
+  int C;
+  long P;
+  const BnPlan plan = bn_check("bn_fwd", x, g, b, &C, &P);
   auto opts = x.options().dtype(torch::kFloat32);
   // out (optional): a channel-narrow channels-last view — the apply
   // writes straight into the caller's concat buffer (strided store)
   long ldo = C;
   torch::Tensor y;
   if (out.numel() > 0) {
-    TORCH_CHECK(cl_narrow(out, &ldo) && out.sizes() == x.sizes() &&
+    TORCH_CHECK(out.is_cuda() && cl_narrow(out, &ldo) &&
+                out.sizes() == x.sizes() &&
                 out.scalar_type() == torch::kBFloat16,
                 "bn_fwd: out must be a bf16 channels-last (or channel-"
                 "narrow) tensor with x's shape");
@@ -966,11 +999,11 @@ std::vector<torch::Tensor> bn_fwd(torch::Tensor x, torch::Tensor g,
   }
   auto mean = torch::empty({C}, opts);
   auto invstd = torch::empty({C}, opts);
-  auto part = torch::empty({(long)Z * C * 2}, opts);
+  auto part = torch::empty({(long)plan.Z * C * 2}, opts);
   launch_bn_fwd((const bf16_t*)x.data_ptr(), (const bf16_t*)g.data_ptr(),
                 (const bf16_t*)b.data_ptr(), (bf16_t*)y.data_ptr(), ldo,
                 mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                part.data_ptr<float>(), P, C, Z, (float)eps, relu,
+                part.data_ptr<float>(), P, C, plan, (float)eps, relu,
                 cur_stream());
   return {y, mean, invstd};
 }
@@ -979,18 +1012,22 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor x, torch::Tensor dy,
                                   torch::Tensor g, torch::Tensor b,
                                   torch::Tensor mean, torch::Tensor invstd,
                                   bool relu) {
-  long ldy = 0;
-  TORCH_CHECK(is_cl(x), "bn_bwd: channels-last x required");
-  TORCH_CHECK(cl_narrow(dy, &ldy), "bn_bwd: dy must be channels-last or a "
+  int C;
+  long P, ldy = 0;
+  const BnPlan plan = bn_check("bn_bwd", x, g, b, &C, &P);
+  TORCH_CHECK(dy.is_cuda() && cl_narrow(dy, &ldy) &&
+              dy.sizes() == x.sizes() &&
+              dy.scalar_type() == torch::kBFloat16,
+              "bn_bwd: dy must be bf16 with x's shape, channels-last or a "
               "channel-narrow view of a channels-last tensor");
-  const int C = x.size(1);
-  const long P = x.numel() / C;
-  const int Z = bn_stats_slices(P, C);
+  TORCH_CHECK(bn_is_vec(mean, torch::kFloat32, C) &&
+              bn_is_vec(invstd, torch::kFloat32, C),
+              "bn_bwd: mean/invstd must be fp32 [C]");
   auto opts = x.options().dtype(torch::kFloat32);
   auto dx = torch::empty_like(x);
   auto dgamma = torch::empty({C}, x.options());
   auto dbeta = torch::empty({C}, x.options());
-  auto part = torch::empty({(long)Z * C * 2}, opts);
+  auto part = torch::empty({(long)plan.Z * C * 2}, opts);
   auto s1n = torch::empty({C}, opts);
   auto s2n = torch::empty({C}, opts);
   launch_bn_bwd((const bf16_t*)x.data_ptr(), (const bf16_t*)dy.data_ptr(),
@@ -998,225 +1035,144 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor x, torch::Tensor dy,
                 mean.data_ptr<float>(), invstd.data_ptr<float>(),
                 (bf16_t*)dx.data_ptr(), (bf16_t*)dgamma.data_ptr(),
                 (bf16_t*)dbeta.data_ptr(), part.data_ptr<float>(),
-                s1n.data_ptr<float>(), s2n.data_ptr<float>(), P, C, Z,
+                s1n.data_ptr<float>(), s2n.data_ptr<float>(), P, C, plan,
                 relu, cur_stream());
   return {dx, dgamma, dbeta};
 }
 
-
-// grouped BN: ONE stats/finalize/apply launch triple for all terminal
+// grouped BN: ONE stats/finalize/apply launch triple for all parallel
 // BNs of an Inception block (per-channel math — identical results to
-// separate per-branch BNs, ~6x fewer launches per block)
+// separate per-branch BNs, ~6x fewer launches per block).
+//
+// Validates every branch of either direction and fills the launch
+// descriptor. views holds the forward's outs or the backward's dys: bf16
+// channels-last or channel-narrow views, either one per branch of that
+// branch's shape (inner-stage BNs whose results feed different
+// consumers), or a single one over all branches' channels side by side
+// (terminal BNs: the block's concat buffer), which is sliced here.
+static BnGroup bn_group_args(const char* who, bool bwd,
+                             const std::vector<torch::Tensor>& xs,
+                             const std::vector<torch::Tensor>& gs,
+                             const std::vector<torch::Tensor>& bs,
+                             const std::vector<torch::Tensor>& views,
+                             long* P, int* ctot) {
+  BnGroup gr = {};
+  const size_t n = xs.size();
+  const char* vname = bwd ? "dy" : "out";
+  TORCH_CHECK(n >= 1 && n <= 8 && gs.size() == n && bs.size() == n &&
+              (views.size() == n || views.size() == 1), who,
+              ": 1..8 branches, one g and b per branch, and one ", vname,
+              " per branch or one over all");
+  const bool joined = views.size() != n;
+  gr.n = (int)n;
+  *P = 0;
+  *ctot = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const auto& x = xs[i];
+    TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.numel() > 0 && is_cl(x) &&
+                x.scalar_type() == torch::kBFloat16 &&
+                (x.size(1) & 7) == 0 &&
+                x.size(1) <= bn_group_max_channels() &&
+                (i == 0 || x.numel() / x.size(1) == *P),
+                who, ": branch inputs must be bf16 channels-last with equal "
+                "spatial size, C%8==0, C<=", bn_group_max_channels());
+    const int C = (int)x.size(1);
+    *P = x.numel() / C;
+    TORCH_CHECK(bn_flat_ok(*P, C), who, ": P*C >= 2^31 (flat-walk index "
+                "bound)");
+    TORCH_CHECK(bn_is_vec(gs[i], torch::kBFloat16, C) &&
+                bn_is_vec(bs[i], torch::kBFloat16, C),
+                who, ": g/b must be bf16 [C] per branch");
+    long ld = 0;
+    const auto& v = views[joined ? 0 : i];
+    TORCH_CHECK(v.is_cuda() && cl_narrow(v, &ld) &&
+                v.scalar_type() == torch::kBFloat16 &&
+                v.size(0) == x.size(0) && v.size(2) == x.size(2) &&
+                v.size(3) == x.size(3) && (joined || v.size(1) == C),
+                who, ": ", vname, " must be a bf16 channels-last (or "
+                "channel-narrow) view of its branch's shape");
+    gr.C[i] = C;
+    gr.x[i] = (const bf16_t*)x.data_ptr();
+    gr.g[i] = (const bf16_t*)gs[i].data_ptr();
+    gr.b[i] = (const bf16_t*)bs[i].data_ptr();
+    bf16_t* vp = (bf16_t*)v.data_ptr() + (joined ? *ctot : 0);
+    if (bwd) {
+      gr.dy[i] = vp;
+      gr.dyld[i] = ld;
+    } else {
+      gr.y[i] = vp;
+      gr.yld[i] = ld;
+    }
+    *ctot += C;
+  }
+  TORCH_CHECK(!joined || views[0].size(1) == *ctot, who, ": the joined ",
+              vname, " must hold the branches' channels, ", *ctot);
+  return gr;
+}
+
+// outs empty: allocate dense per-branch outputs and return them ahead of
+// mean and invstd; otherwise write into outs (one per branch, or one
+// joined view) and return {mean, invstd}
 std::vector<torch::Tensor> bn_group_fwd(std::vector<torch::Tensor> xs,
                                         std::vector<torch::Tensor> gs,
                                         std::vector<torch::Tensor> bs,
-                                        torch::Tensor out, double eps,
-                                        bool relu) {
-  const int n = (int)xs.size();
-  TORCH_CHECK(n >= 1 && n <= 8 && (int)gs.size() == n &&
-              (int)bs.size() == n, "bn_group: 1..8 branches");
-  const bf16_t* xp[8];
-  const bf16_t* gp[8];
-  const bf16_t* bp[8];
-  int Cs[8];
-  int ctot = 0;
-  const long P = xs[0].numel() / xs[0].size(1);
-  for (int i = 0; i < n; ++i) {
-    auto& x = xs[i];
-    TORCH_CHECK(x.is_cuda() && x.dim() == 4 && is_cl(x) &&
-                x.scalar_type() == torch::kBFloat16 &&
-                x.numel() / x.size(1) == P && (x.size(1) & 7) == 0 &&
-                x.size(1) <= 512,
-                "bn_group_fwd: branch inputs must be bf16 channels-last "
-                "with equal spatial size, C%8==0, C<=512");
-    Cs[i] = (int)x.size(1);
-    TORCH_CHECK(gs[i].numel() == Cs[i] && bs[i].numel() == Cs[i] &&
-                gs[i].scalar_type() == torch::kBFloat16 &&
-                bs[i].scalar_type() == torch::kBFloat16, "bad g/b");
-    xp[i] = (const bf16_t*)x.data_ptr();
-    gp[i] = (const bf16_t*)gs[i].data_ptr();
-    bp[i] = (const bf16_t*)bs[i].data_ptr();
-    ctot += Cs[i];
+                                        std::vector<torch::Tensor> outs,
+                                        double eps, bool relu) {
+  std::vector<torch::Tensor> ret;
+  if (outs.empty()) {
+    for (auto& x : xs) ret.push_back(torch::empty_like(x));
+    outs = ret;
   }
-  long ldo = ctot;
-  TORCH_CHECK(cl_narrow(out, &ldo) && out.size(1) == ctot &&
-              out.numel() / out.size(1) == P &&
-              out.scalar_type() == torch::kBFloat16,
-              "bn_group_fwd: out must be a bf16 channels-last (or "
-              "channel-narrow) [N,Ctot,H,W] view");
-  const int Z = bn_group_slices(P, Cs, n);
+  long P;
+  int ctot;
+  const BnGroup gr = bn_group_args("bn_group_fwd", false, xs, gs, bs, outs,
+                                   &P, &ctot);
+  const int Z = bn_group_slices(P, gr.C, gr.n);
   auto opts = xs[0].options().dtype(torch::kFloat32);
   auto mean = torch::empty({ctot}, opts);
   auto invstd = torch::empty({ctot}, opts);
   auto part = torch::empty({(long)Z * ctot * 2}, opts);
-  bf16_t* youts[8];
-  long ylds[8];
-  int coff = 0;
-  for (int i = 0; i < n; ++i) {
-    youts[i] = (bf16_t*)out.data_ptr() + coff;
-    ylds[i] = ldo;
-    coff += Cs[i];
-  }
-  launch_bn_group_fwd(xp, gp, bp, Cs, n, youts, ylds,
-                      mean.data_ptr<float>(), invstd.data_ptr<float>(),
+  launch_bn_group_fwd(gr, mean.data_ptr<float>(), invstd.data_ptr<float>(),
                       part.data_ptr<float>(), P, Z, (float)eps, relu,
                       cur_stream());
-  return {mean, invstd};
+  ret.push_back(mean);
+  ret.push_back(invstd);
+  return ret;
 }
 
-// per-branch DENSE outputs (parallel inner-stage BNs whose results
-// feed different consumers): same grouped kernels, one launch triple
-std::vector<torch::Tensor> bn_group_fwd_multi(std::vector<torch::Tensor> xs,
-                                              std::vector<torch::Tensor> gs,
-                                              std::vector<torch::Tensor> bs,
-                                              double eps, bool relu) {
-  const int n = (int)xs.size();
-  TORCH_CHECK(n >= 1 && n <= 8, "bn_group: 1..8 branches");
-  const bf16_t* xp[8];
-  const bf16_t* gp[8];
-  const bf16_t* bp[8];
-  bf16_t* youts[8];
-  long ylds[8];
-  int Cs[8];
-  int ctot = 0;
-  const long P = xs[0].numel() / xs[0].size(1);
-  std::vector<torch::Tensor> outs;
-  for (int i = 0; i < n; ++i) {
-    auto& x = xs[i];
-    TORCH_CHECK(x.is_cuda() && x.dim() == 4 && is_cl(x) &&
-                x.scalar_type() == torch::kBFloat16 &&
-                x.numel() / x.size(1) == P && (x.size(1) & 7) == 0 &&
-                x.size(1) <= 512, "bn_group_fwd_multi: bad branch input");
-    Cs[i] = (int)x.size(1);
-    xp[i] = (const bf16_t*)x.data_ptr();
-    gp[i] = (const bf16_t*)gs[i].data_ptr();
-    bp[i] = (const bf16_t*)bs[i].data_ptr();
-    auto y = torch::empty_like(x);
-    youts[i] = (bf16_t*)y.data_ptr();
-    ylds[i] = Cs[i];
-    outs.push_back(y);
-    ctot += Cs[i];
-  }
-  const int Z = bn_group_slices(P, Cs, n);
-  auto opts = xs[0].options().dtype(torch::kFloat32);
-  auto mean = torch::empty({ctot}, opts);
-  auto invstd = torch::empty({ctot}, opts);
-  auto part = torch::empty({(long)Z * ctot * 2}, opts);
-  launch_bn_group_fwd(xp, gp, bp, Cs, n, youts, ylds,
-                      mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                      part.data_ptr<float>(), P, Z, (float)eps, relu,
-                      cur_stream());
-  outs.push_back(mean);
-  outs.push_back(invstd);
-  return outs;
-}
-
+// returns the per-branch dense dx, then dgamma and dbeta over all channels
 std::vector<torch::Tensor> bn_group_bwd(std::vector<torch::Tensor> xs,
-                                        torch::Tensor dy,
+                                        std::vector<torch::Tensor> dys,
                                         std::vector<torch::Tensor> gs,
                                         std::vector<torch::Tensor> bs,
                                         torch::Tensor mean,
                                         torch::Tensor invstd, bool relu) {
-  const int n = (int)xs.size();
-  TORCH_CHECK(n >= 1 && n <= 8, "bn_group: 1..8 branches");
-  const bf16_t* xp[8];
-  const bf16_t* gp[8];
-  const bf16_t* bp[8];
-  bf16_t* dxp[8];
-  int Cs[8];
-  int ctot = 0;
-  const long P = xs[0].numel() / xs[0].size(1);
-  std::vector<torch::Tensor> outs;
-  for (int i = 0; i < n; ++i) {
-    Cs[i] = (int)xs[i].size(1);
-    xp[i] = (const bf16_t*)xs[i].data_ptr();
-    gp[i] = (const bf16_t*)gs[i].data_ptr();
-    bp[i] = (const bf16_t*)bs[i].data_ptr();
-    auto dx = torch::empty_like(xs[i]);
-    dxp[i] = (bf16_t*)dx.data_ptr();
-    outs.push_back(dx);
-    ctot += Cs[i];
+  long P;
+  int ctot;
+  BnGroup gr = bn_group_args("bn_group_bwd", true, xs, gs, bs, dys, &P,
+                             &ctot);
+  TORCH_CHECK(bn_is_vec(mean, torch::kFloat32, ctot) &&
+              bn_is_vec(invstd, torch::kFloat32, ctot),
+              "bn_group_bwd: mean/invstd must be fp32 [sum C]");
+  std::vector<torch::Tensor> ret;
+  for (int i = 0; i < gr.n; ++i) {
+    ret.push_back(torch::empty_like(xs[i]));
+    gr.dx[i] = (bf16_t*)ret[i].data_ptr();
   }
-  long ldy = ctot;
-  TORCH_CHECK(dy.is_cuda() && cl_narrow(dy, &ldy) && dy.size(1) == ctot,
-              "bn_group_bwd: dy must be channels-last or channel-narrow");
-  const bf16_t* dys[8];
-  long dylds[8];
-  int coff = 0;
-  for (int i = 0; i < n; ++i) {
-    dys[i] = (const bf16_t*)dy.data_ptr() + coff;
-    dylds[i] = ldy;
-    coff += Cs[i];
-  }
-  const int Z = bn_group_slices(P, Cs, n);
+  const int Z = bn_group_slices(P, gr.C, gr.n);
   auto opts = xs[0].options().dtype(torch::kFloat32);
   auto dgamma = torch::empty({ctot}, xs[0].options());
   auto dbeta = torch::empty({ctot}, xs[0].options());
   auto s1n = torch::empty({ctot}, opts);
   auto s2n = torch::empty({ctot}, opts);
   auto part = torch::empty({(long)Z * ctot * 2}, opts);
-  launch_bn_group_bwd(xp, dys, dylds, gp, bp, dxp,
-                      Cs, n, mean.data_ptr<float>(),
-                      invstd.data_ptr<float>(), (bf16_t*)dgamma.data_ptr(),
-                      (bf16_t*)dbeta.data_ptr(), s1n.data_ptr<float>(),
-                      s2n.data_ptr<float>(), part.data_ptr<float>(), P, Z,
-                      relu, cur_stream());
-  outs.push_back(dgamma);
-  outs.push_back(dbeta);
-  return outs;
-}
-
-std::vector<torch::Tensor> bn_group_bwd_multi(std::vector<torch::Tensor> xs,
-                                              std::vector<torch::Tensor> dys_in,
-                                              std::vector<torch::Tensor> gs,
-                                              std::vector<torch::Tensor> bs,
-                                              torch::Tensor mean,
-                                              torch::Tensor invstd,
-                                              bool relu) {
-  const int n = (int)xs.size();
-  TORCH_CHECK(n >= 1 && n <= 8 && (int)dys_in.size() == n,
-              "bn_group: 1..8 branches");
-  const bf16_t* xp[8];
-  const bf16_t* gp[8];
-  const bf16_t* bp[8];
-  bf16_t* dxp[8];
-  const bf16_t* dys[8];
-  long dylds[8];
-  int Cs[8];
-  int ctot = 0;
-  const long P = xs[0].numel() / xs[0].size(1);
-  std::vector<torch::Tensor> outs;
-  for (int i = 0; i < n; ++i) {
-    Cs[i] = (int)xs[i].size(1);
-    xp[i] = (const bf16_t*)xs[i].data_ptr();
-    gp[i] = (const bf16_t*)gs[i].data_ptr();
-    bp[i] = (const bf16_t*)bs[i].data_ptr();
-    long ldy = Cs[i];
-    TORCH_CHECK(cl_narrow(dys_in[i], &ldy) && dys_in[i].size(1) == Cs[i],
-                "bn_group_bwd_multi: bad dy");
-    dys[i] = (const bf16_t*)dys_in[i].data_ptr();
-    dylds[i] = ldy;
-    auto dx = torch::empty_like(xs[i]);
-    dxp[i] = (bf16_t*)dx.data_ptr();
-    outs.push_back(dx);
-    ctot += Cs[i];
-  }
-  const int Z = bn_group_slices(P, Cs, n);
-  auto opts = xs[0].options().dtype(torch::kFloat32);
-  auto dgamma = torch::empty({ctot}, xs[0].options());
-  auto dbeta = torch::empty({ctot}, xs[0].options());
-  auto s1n = torch::empty({ctot}, opts);
-  auto s2n = torch::empty({ctot}, opts);
-  auto part = torch::empty({(long)Z * ctot * 2}, opts);
-  launch_bn_group_bwd(xp, dys, dylds, gp, bp, dxp,
-                      Cs, n, mean.data_ptr<float>(),
-                      invstd.data_ptr<float>(), (bf16_t*)dgamma.data_ptr(),
-                      (bf16_t*)dbeta.data_ptr(), s1n.data_ptr<float>(),
-                      s2n.data_ptr<float>(), part.data_ptr<float>(), P, Z,
-                      relu, cur_stream());
-  outs.push_back(dgamma);
-  outs.push_back(dbeta);
-  return outs;
+  launch_bn_group_bwd(gr, mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                      (bf16_t*)dgamma.data_ptr(), (bf16_t*)dbeta.data_ptr(),
+                      s1n.data_ptr<float>(), s2n.data_ptr<float>(),
+                      part.data_ptr<float>(), P, Z, relu, cur_stream());
+  ret.push_back(dgamma);
+  ret.push_back(dbeta);
+  return ret;
 }
 
 torch::Tensor avg_pool3x3(torch::Tensor x) {
@@ -1519,7 +1475,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool3x3s2_fwd", &maxpool3x3s2_fwd);
   m.def("bn_group_fwd", &bn_group_fwd);
   m.def("bn_group_bwd", &bn_group_bwd);
-  m.def("bn_group_fwd_multi", &bn_group_fwd_multi);
   m.def("gemm_sgd", &gemm_sgd);
   m.def("mlp_tail_sgd", &mlp_tail_sgd);
   m.def("mlp_head_tail_sgd", &mlp_head_tail_sgd);
@@ -1534,8 +1489,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_sgd_plan", &gemm_sgd_plan, py::arg("M"), py::arg("N"),
         py::arg("K"));
   m.def("gemm_vec_levels", &gemm_vec_levels, py::arg("a"), py::arg("b"));
+  // (stats, apply, Z): the kernel family of each BN phase and the slices
+  m.def("bn_plan", &bn_plan_py, py::arg("P"), py::arg("C"));
   m.def("add_n", &add_n);
-  m.def("bn_group_bwd_multi", &bn_group_bwd_multi);
   m.def("maxpool3x3s2_bwd", &maxpool3x3s2_bwd);
   m.def("bn_bwd", &bn_bwd, "fused batch-norm (+relu mask) bwd");
   m.def("conv2d_bwd_data", &conv2d_bwd_data);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""A/B of the sparse kernels between this tree and a second built tree:
-same bits, same speed.
+"""A/B of one kernel family between this tree and a second built tree:
+same bits, same speed. --suite sparse (the default) is described first;
+--suite bn, the batch-norm kernels, at the end.
 
     python tools/sparse_ab.py /path/to/other/tree --out profiles/NAME.txt
 
@@ -34,6 +35,18 @@ spread is the noise of the run; a spread of zero at the printed precision
 counts as one unit of the last digit). A median below the other tree's
 minimum is marked "faster". ``bench.py --workload nmf`` on both trees gives
 the end-to-end lines.
+
+--suite bn. Same bits: bn_fwd then bn_bwd on seeded normal inputs, for the
+shapes of tests/test_kernels_gpu.py (one per kernel path) and one per
+Inception stage, relu on and off, with dense and with channel-narrow out /
+dy; and ops.bn_group_apply (joined) and ops.bn_group_multi over the block-A
+widths at 35 x 35. Saved per case: y, mean, invstd, dx, dgamma, dbeta;
+tensors above 8 MiB as checksums. Same speed: forward and backward of the
+Inception-stage and grouped cases, by the rule above. End to end:
+``bench.py --workload inception`` on both trees, with every array of
+--dump-outputs compared for equality. The other tree runs the same-bits
+cases and the benchmark twice: a case or array that it does not reproduce
+itself (a kernel with a data race) is reported as such and not compared.
 """
 
 import argparse
@@ -55,10 +68,10 @@ DEV = "cuda:0"
 
 # ------------------------------------------------------------------ children
 
-def keep(t):
+def keep(t, big=BIG):
     """What a child saves of a tensor: itself, or two checksums."""
     t = t.contiguous()
-    if t.numel() * t.element_size() <= BIG:
+    if t.numel() * t.element_size() <= big:
         return t.cpu()
     b = t.view(-1).view(torch.uint8)
     if b.numel() % 8:       # zero-pad to whole int64 words
@@ -212,6 +225,134 @@ def child_time(ops, out, min_s):
         json.dump(times, fh)
 
 
+# -------------------------------------------------------------- bn children
+
+BN_BIG = 8 << 20
+BN_UNIT = [(4, 16, 14, 14), (2, 64, 35, 35), (8, 32, 7, 9), (1, 7, 5, 5),
+           (2, 20, 5, 7), (4, 48, 104, 104), (2, 256, 64, 64),
+           (2, 2048, 72, 72)]
+BN_STAGES = [(32, 32, 147, 147), (32, 192, 35, 35), (32, 768, 17, 17),
+             (32, 2048, 8, 8)]
+BN_GROUP = (32, [64, 64, 96, 32], 35, 35)       # Inception block A
+
+
+def cl_randn(gen, shape, narrow=False):
+    """Seeded normal bf16 NCHW tensor in channels-last memory; narrow: as a
+    channel slice of a wider buffer (kept 16-byte aligned when C % 8 == 0)."""
+    N, C, H, W = shape
+    pad, off = (16, 8) if C % 8 == 0 else (5, 3)
+    wide = C + pad if narrow else C
+    t = torch.randn(N, H, W, wide, device=DEV, generator=gen).to(
+        torch.bfloat16).permute(0, 3, 1, 2)
+    return t.narrow(1, off, C) if narrow else t
+
+
+def bn_params(gen, C):
+    g = (torch.rand(C, device=DEV, generator=gen) + 0.5).to(torch.bfloat16)
+    b = (torch.randn(C, device=DEV, generator=gen) * 0.2).to(torch.bfloat16)
+    return g, b
+
+
+def bn_single(ext, gen, shape, relu, narrow):
+    """bn_fwd + bn_bwd -> [y, mean, invstd, dx, dgamma, dbeta]."""
+    x = cl_randn(gen, shape)
+    g, b = bn_params(gen, shape[1])
+    out = cl_randn(gen, shape, True) if narrow else \
+        torch.empty(0, device=DEV, dtype=torch.bfloat16)
+    dy = cl_randn(gen, shape, narrow)
+    y, mean, invstd = ext.bn_fwd(x, g, b, 1e-3, relu, out)
+    return [y, mean, invstd] + list(ext.bn_bwd(x, dy, g, b, mean, invstd,
+                                               relu))
+
+
+def bn_group_case(gen, joined):
+    """Inputs of one grouped case: (xs, ws, bs), the view a joined forward
+    writes into (a channel-narrow slice of a wider concat buffer; None for
+    multi) and seeded gradients for the output(s)."""
+    N, Cs, H, W = BN_GROUP
+    xs = [cl_randn(gen, (N, c, H, W)).requires_grad_(True) for c in Cs]
+    ps = [bn_params(gen, c) for c in Cs]
+    ws = [g.requires_grad_(True) for g, _ in ps]
+    bs = [b.requires_grad_(True) for _, b in ps]
+    if joined:
+        view = cl_randn(gen, (N, sum(Cs) + 64, H, W)).narrow(1, 32, sum(Cs))
+        dys = [cl_randn(gen, (N, sum(Cs), H, W), True)]
+    else:
+        view = None
+        dys = [cl_randn(gen, (N, c, H, W), i % 2 == 1)
+               for i, c in enumerate(Cs)]
+    return (xs, ws, bs), view, dys
+
+
+def bn_group_fwd(ops, inputs, view, relu):
+    if view is not None:
+        return [ops.bn_group_apply(view, *inputs, eps=1e-3, relu=relu)]
+    return list(ops.bn_group_multi(*inputs, eps=1e-3, relu=relu))
+
+
+def bn_child_check(ops, out):
+    ext = ops._ext()
+    saved = {}
+    for shape in BN_UNIT + BN_STAGES:
+        for relu in (False, True):
+            for narrow in (False, True):
+                gen = torch.Generator(device=DEV).manual_seed(
+                    2000 + shape[1] + shape[2])
+                saved["%s relu=%d %s" % (shape, relu, "narrow" if narrow
+                                         else "dense")] = \
+                    [keep(t, BN_BIG) for t in bn_single(ext, gen, shape, relu,
+                                                        narrow)]
+    for relu in (False, True):
+        for joined in (True, False):
+            gen = torch.Generator(device=DEV).manual_seed(3000)
+            inputs, view, dys = bn_group_case(gen, joined)
+            ys = bn_group_fwd(ops, inputs, view, relu)
+            mean, invstd = ys[0].grad_fn.saved_tensors[:2]
+            grads = torch.autograd.grad(ys, sum(inputs, []), dys)
+            saved["group %s relu=%d" % ("joined" if joined else "multi",
+                                        relu)] = \
+                [keep(t, BN_BIG) for t in ys + [mean, invstd] + list(grads)]
+    torch.cuda.synchronize()
+    torch.save(saved, out)
+
+
+def bn_child_time(ops, out, min_s):
+    ext = ops._ext()
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    none = torch.empty(0, device=DEV, dtype=torch.bfloat16)
+    rows = []
+    for shape in BN_STAGES:
+        x, dy = cl_randn(gen, shape), cl_randn(gen, shape)
+        g, b = bn_params(gen, shape[1])
+        _, mean, invstd = ext.bn_fwd(x, g, b, 1e-3, True, none)
+        rows += [
+            ("fwd %dx%dx%dx%d" % shape,
+             lambda x=x, g=g, b=b: ext.bn_fwd(x, g, b, 1e-3, True, none)),
+            ("bwd %dx%dx%dx%d" % shape,
+             lambda x=x, dy=dy, g=g, b=b, mean=mean, invstd=invstd:
+             ext.bn_bwd(x, dy, g, b, mean, invstd, True))]
+    for joined in (True, False):
+        name = "group %s %s" % ("joined" if joined else "multi",
+                                "+".join(map(str, BN_GROUP[1])))
+        inputs, view, dys = bn_group_case(gen, joined)
+        ys = bn_group_fwd(ops, inputs, view, True)
+        rows += [
+            ("fwd " + name,
+             lambda inputs=inputs, view=view: bn_group_fwd(ops, inputs, view,
+                                                           True)),
+            ("bwd " + name,
+             lambda ys=ys, dys=dys, inputs=inputs: torch.autograd.grad(
+                 ys, sum(inputs, []), dys, retain_graph=True))]
+    times = {}
+    for label, fn in rows:
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        times[label] = window(fn, min_s)
+    with open(out, "w") as fh:
+        json.dump(times, fh)
+
+
 def child(args):
     sys.path.insert(0, args.tree)
     from tfmesos_amd import ops
@@ -219,10 +360,53 @@ def child(args):
         os.path.abspath(args.tree) + os.sep), ops.__file__
     ops._ext()      # raise now if the tree is not built
     assert torch.cuda.is_available(), "sparse_ab needs a GPU"
+    suite = SUITES[args.suite]
     if args.child == "check":
-        child_check(ops, args.child_out)
+        suite["check"](ops, args.child_out)
     else:
-        child_time(ops, args.child_out, args.window)
+        suite["time"](ops, args.child_out, args.window)
+
+
+def nmf_bench(args, dump):
+    return ["--workload", "nmf", "--steps", str(args.nmf_steps), "--warmup",
+            "50"]
+
+
+def inception_bench(args, dump):
+    return ["--workload", "inception", "--steps", "20", "--warmup", "5",
+            "--dump-outputs", dump]
+
+
+def same_dumps(tmp):
+    """Compare the trees' --dump-outputs arrays: (report line, differ). An
+    array that two runs of the other tree do not reproduce is left out."""
+    import numpy as np
+    dirs = [os.path.join(tmp, "dump_" + t) for t in ("other", "this",
+                                                     "other again")]
+    names = sorted(os.listdir(dirs[0]))
+    assert names and all(names == sorted(os.listdir(d)) for d in dirs[1:])
+
+    def differ(a, b):
+        return [n for n in names if not np.array_equal(
+            np.load(os.path.join(a, n)), np.load(os.path.join(b, n)))]
+    unstable = differ(dirs[0], dirs[2])
+    diff = [n for n in differ(dirs[0], dirs[1]) if n not in unstable]
+    return ("--dump-outputs: %d arrays compared for equality; %d differ%s; "
+            "%d left out, which two runs of the other tree do not "
+            "reproduce%s"
+            % (len(names), len(diff), "".join(" " + n for n in diff),
+               len(unstable), "".join(" " + n for n in unstable)), len(diff))
+
+
+SUITES = {
+    "sparse": dict(
+        title="sparse kernels", check=child_check, time=child_time, big=BIG,
+        speed="4M x 256 table, n = 1M, D = 256", bench=nmf_bench),
+    "bn": dict(
+        title="batch-norm kernels", check=bn_child_check, time=bn_child_time,
+        big=BN_BIG, speed="Inception-stage layers and block-A groups, relu",
+        bench=inception_bench, dumps=same_dumps, repeat=True),
+}
 
 
 # -------------------------------------------------------------------- parent
@@ -243,8 +427,8 @@ def run(cmd, cwd, limit):
 def run_child(kind, tree, out, args):
     print("sparse_ab: %s child on %s" % (kind, tree), flush=True)
     run([sys.executable, os.path.abspath(__file__), tree, "--child", kind,
-         "--child-out", out, "--window", str(args.window)], tree,
-        args.child_timeout)
+         "--child-out", out, "--window", str(args.window), "--suite",
+         args.suite], tree, args.child_timeout)
 
 
 def fmt_ms(s):
@@ -262,41 +446,55 @@ def main():
     ap.add_argument("--label", default=None,
                     help="what the other tree is, for the report's first "
                          "line (default: its path)")
-    ap.add_argument("--child",choices=["check", "time"], default=None)
+    ap.add_argument("--suite", choices=["sparse", "bn"], default="sparse")
+    ap.add_argument("--child", choices=["check", "time"], default=None)
     ap.add_argument("--child-out", default=None)
     args = ap.parse_args()
     args.tree = os.path.abspath(args.tree)
     if args.child:
         return child(args)
+    suite = SUITES[args.suite]
     trees = [("other", args.tree), ("this", HERE)]
-    lines = ["sparse kernels, this tree against %s (\"other\")"
-             % (args.label or args.tree)]
+    lines = ["%s, this tree against %s (\"other\")"
+             % (suite["title"], args.label or args.tree)]
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
         saved = {}
-        for label, tree in trees:
-            path = os.path.join(tmp, "check_%s.pt" % label)
+        runs = trees + [("other again", args.tree)] * bool(suite.get("repeat"))
+        for label, tree in runs:
+            path = os.path.join(tmp, "check.pt")
             run_child("check", tree, path, args)
             saved[label] = torch.load(path)
             os.remove(path)
         a, b = saved["other"], saved["this"]
-        assert a.keys() == b.keys()
-        whole = sums = 0
+        again = saved.get("other again", a)
+        assert a.keys() == b.keys() == again.keys()
+
+        def differing(p, q):
+            """Indices of the tensors (or checksum pairs) that differ."""
+            assert len(p) == len(q)
+            return [i for i, (x, y) in enumerate(zip(p, q)) if not torch.equal(
+                *((x[1], y[1]) if isinstance(x, tuple) else (x, y)))]
+        whole = sums = unstable = 0
         for k in a:
-            assert len(a[k]) == len(b[k])
-            for i, (x, y) in enumerate(zip(a[k], b[k])):
-                if isinstance(x, tuple):    # too large to save: checksums
-                    sums += 1
-                    x, y = x[1], y[1]
-                else:
-                    whole += 1
-                if not torch.equal(x, y):
-                    bad += 1
-                    lines.append("DIFFERENT: %s, tensor %d" % (k, i))
-        lines.append("same bits: %d cases; %d tensors compared whole with "
-                     "torch.equal, %d tensors above %d MiB by their two int64 "
-                     "checksums; %d differ"
-                     % (len(a), whole, sums, BIG >> 20, bad))
+            if differing(a[k], again[k]):
+                unstable += 1
+                lines.append("NOT REPRODUCED by two runs of the other tree, "
+                             "left out: %s (tensors %s; this tree against the "
+                             "first run: %s)" % (k, differing(a[k], again[k]),
+                                                 differing(a[k], b[k])))
+                continue
+            n = sum(isinstance(x, tuple) for x in a[k])
+            sums += n
+            whole += len(a[k]) - n
+            for i in differing(a[k], b[k]):
+                bad += 1
+                lines.append("DIFFERENT: %s, tensor %d" % (k, i))
+        lines.append("same bits: %d cases, %d more left out; %d tensors "
+                     "compared whole with torch.equal, %d tensors above %d "
+                     "MiB by their two int64 checksums; %d differ"
+                     % (len(a) - unstable, unstable, whole, sums,
+                        suite["big"] >> 20, bad))
         del saved, a, b
         times = {label: {} for label, _ in trees}
         for r in range(args.reps):          # the trees alternate
@@ -306,9 +504,16 @@ def main():
                 with open(path) as fh:
                     for k, v in json.load(fh).items():
                         times[label].setdefault(k, []).append(v)
-    lines += ["", "same speed: 4M x 256 table, n = 1M, D = 256, %s; window >= "
+        bench = {label: suite["bench"](
+            args, os.path.join(tmp, "dump_" + label)) for label, _ in runs}
+        outs = {label: run([sys.executable, "bench.py", "--gpus", "1"]
+                           + bench[label], tree, args.child_timeout)
+                for label, tree in runs}
+        dumps = suite["dumps"](tmp) if "dumps" in suite else None
+    lines += ["", "same speed: %s, %s; window >= "
               "%.2f s, %d alternating rounds of one process per tree"
-              % (torch.cuda.get_device_name(0), args.window, args.reps),
+              % (suite["speed"], torch.cuda.get_device_name(0), args.window,
+                 args.reps),
               "%-36s %10s %17s %10s %17s  %s"
               % ("ms/call", "other med", "min-max", "this med", "min-max",
                  "verdict")]
@@ -324,13 +529,14 @@ def main():
                      % (k, fmt_ms(omed), "%s-%s" % (fmt_ms(o[0]), fmt_ms(o[-1])),
                         fmt_ms(tmed), "%s-%s" % (fmt_ms(t[0]), fmt_ms(t[-1])),
                         verdict))
-    lines += ["", "bench.py --gpus 1 --workload nmf --steps %d --warmup 50"
-              % args.nmf_steps]
-    for label, tree in trees:
-        outp = run([sys.executable, "bench.py", "--gpus", "1", "--workload",
-                    "nmf", "--steps", str(args.nmf_steps), "--warmup", "50"],
-                   tree, args.child_timeout)
-        lines.append("%-5s %s" % (label, outp.strip().splitlines()[-1]))
+    lines += ["", "bench.py --gpus 1 " + " ".join(
+        "DIR" if a.startswith(tmp) else a for a in bench["this"])]
+    for label, _ in runs:
+        lines.append("%-11s %s" % (label,
+                                   outs[label].strip().splitlines()[-1]))
+    if dumps:
+        lines.append(dumps[0])
+        bad += dumps[1]
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     if args.out:
