@@ -1985,12 +1985,12 @@ def mlp_head_tail_grads(x, h, w2, b2, y, dw1, db1, dw2, db2):
     """Classifier head + dW1 tail in ONE kernel (GPU, csrc/gemm.hip
     mlp_head_tail_kernel): every block of the dW1 = x^T @ dh GEMM
     recomputes the logits / softmax / dh slice it consumes, so dh never
-    touches global memory; block (0,0) also produces dW2, db2 and the
-    loss. Fills dw1, db1, dw2, db2 (one dtype, fp32 or bf16) and returns
-    the mean loss — bit-identical to mlp_head_fused + gemm_bias_act's
-    dW1 GEMM (the small-tile kernel's sum order from 32 tiles up, the
-    64x64 kernel's below). Limits: B<=128, H<=128 (H%4==0), C<=16,
-    2..512 32x32 tiles. CPU: composed fp32 reference."""
+    touches global memory; blocks of their own produce db1, dW2, and db2
+    with the loss. Fills dw1, db1, dw2, db2 (one dtype, fp32 or bf16)
+    and returns the mean loss — bit-identical to mlp_head_fused +
+    gemm_bias_act's dW1 GEMM (the small-tile kernel's sum order from 32
+    tiles up, the 64x64 kernel's below). Limits: B<=128, H<=128
+    (H%4==0), C<=16, 2..512 32x32 tiles. CPU: composed fp32 reference."""
     if x.is_cuda:
         return _ext().mlp_head_tail_grads(x, h, w2, b2, y, dw1, db1,
                                           dw2, db2)

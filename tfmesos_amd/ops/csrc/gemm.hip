@@ -887,18 +887,37 @@ DEVINL void small_sgd_fetch(const SmallSgd& sg, SmallSgdPre& pre, bool cs,
 
 // small_sgd_fetch for the fused head+tail kernel (ldc == N): the same
 // elements, range-checked instead of clamped. Row m >= M lies beyond
-// the extent together with every column n < N.
-DEVINL void small_sgd_fetch_buf(const SmallSgd& sg, SmallSgdPre& pre, int m0,
-                                int n0, int M, int N, int w, int lane) {
+// the extent together with every column n < N. In two parts, W1 and
+// b1: the kernel's block roles each fetch what they apply.
+DEVINL void small_sgd_fetch_buf_w(const SmallSgd& sg, SmallSgdPre& pre,
+                                  int m0, int n0, int M, int N, int w,
+                                  int lane) {
   const brsrc_t wr = buf_rsrc(sg.pmw, M * N * 4);
   const int n = n0 + (lane & 31);
   const int nb = n < N ? n * 4 : BUF_OOB;
 #pragma unroll
   for (int u = 0; u < 4; ++u)
     pre.w[u] = buf_f32(wr, nb + small_sgd_row(m0, w, u, lane) * N * 4);
-  pre.b = 0.f;
-  if (blockIdx.x == 0 && sg.pmb != nullptr)
-    pre.b = buf_f32(buf_rsrc(sg.pmb, N * 4), n * 4);
+}
+
+DEVINL void small_sgd_fetch_buf_b(const SmallSgd& sg, SmallSgdPre& pre,
+                                  int n0, int N, int lane) {
+  if (sg.pmb != nullptr)
+    pre.b = buf_f32(buf_rsrc(sg.pmb, N * 4), (n0 + (lane & 31)) * 4);
+}
+
+// small_sgd_commit's bias half on its own (wave 0, lanes 0..31)
+DEVINL void small_sgd_commit_b(const SmallSgd& sg, const SmallSgdPre& pre,
+                               const float (*csred)[32], int n0, int N,
+                               int lane) {
+  const int nn = n0 + lane;
+  if (nn < N && sg.pmb != nullptr) {
+    const float sv = csred[0][lane] + csred[1][lane] + csred[2][lane] +
+                     csred[3][lane];
+    const float pv = pre.b - sg.lr * sv;
+    sg.pmb[nn] = pv;
+    sg.psb[nn] = f2bf(pv);
+  }
 }
 
 DEVINL void small_sgd_commit(const SmallSgd& sg, const SmallSgdPre& pre,
@@ -920,15 +939,19 @@ DEVINL void small_sgd_commit(const SmallSgd& sg, const SmallSgdPre& pre,
       sg.psw[idx] = f2bf(pv);
     }
   }
-  if (cs && w == 0 && blockIdx.x == 0 && lane < 32) {
-    const int nn = n0 + lane;
-    if (nn < N && sg.pmb != nullptr) {
-      const float sv = csred[0][lane] + csred[1][lane] + csred[2][lane] +
-                       csred[3][lane];
-      const float pv = pre.b - sg.lr * sv;
-      sg.pmb[nn] = pv;
-      sg.psb[nn] = f2bf(pv);
-    }
+  if (cs && w == 0 && blockIdx.x == 0 && lane < 32)
+    small_sgd_commit_b(sg, pre, csred, n0, N, lane);
+}
+
+// the colsum store of one N tile (wave 0, lanes 0..31)
+DEVINL void small_store_cs(const float (*csred)[32], void* colsum_out,
+                           bool cs_f32, int n0, int N, int lane) {
+  const int nn = n0 + lane;
+  if (nn < N) {
+    const float sv = csred[0][lane] + csred[1][lane] + csred[2][lane] +
+                     csred[3][lane];
+    if (cs_f32) ((float*)colsum_out)[nn] = sv;
+    else ((__bf16*)colsum_out)[nn] = (__bf16)sv;
   }
 }
 
@@ -961,15 +984,8 @@ DEVINL void small_store(const float (*red)[64 * 16],
       else ((__bf16*)Cout)[(long)m * ldc + n] = (__bf16)x;
     }
   }
-  if (cs && blockIdx.x == 0 && lane < 32) {
-    const int nn = n0 + lane;
-    if (nn < N) {
-      const float sv = csred[0][lane] + csred[1][lane] + csred[2][lane] +
-                       csred[3][lane];
-      if (cs_f32) ((float*)colsum_out)[nn] = sv;
-      else ((__bf16*)colsum_out)[nn] = (__bf16)sv;
-    }
-  }
+  if (cs && blockIdx.x == 0 && lane < 32)
+    small_store_cs(csred, colsum_out, cs_f32, n0, N, lane);
 }
 
 template <bool TA, bool CS>
@@ -1225,10 +1241,11 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
 // the full hs/dls images every block holds after the barrier (same
 // MFMA order over rows and the same 16-partial db2 order as the head;
 // the transposed fragments come from the row-major images via
-// ds_read_b64_tr_b16). !APPLY: block (0,0) stores them. APPLY: every
-// block read the live W2/b2 shadow at its start, so they may only be
-// overwritten once all blocks have read — an arrival ticket without
-// any spinning picks the block that arrives last: after the barrier
+// ds_read_b64_tr_b16). !APPLY: classifier blocks of their own store
+// them (block roles, below). APPLY: every block read the live W2/b2
+// shadow at its start, so they may only be overwritten once all blocks
+// have read — an arrival ticket without any spinning picks the block
+// that arrives last: after the barrier
 // (all four waves' W2/b2 loads have landed in LDS) one lane draws an
 // agent-scope fetch_add ticket, the block applies its own W1 tile
 // while the ticket is in flight, and whoever drew nblocks-1 does the
@@ -1238,10 +1255,11 @@ void gemm_small_kernel(const __bf16* __restrict__ A,
 // that needs none): the classifier work is serialized behind the last
 // arrival. So where the step's preceding launch can take a 2 KB
 // snapshot of W2/b2 (the small stripe reduce, SnapJob), the kernel
-// reads the snapshot instead (ticket == null) and a fixed block
-// applies to the live shadow concurrently — no atomics at all. The
-// ticket stays for shapes whose fwd GEMM takes no snapshot. (The
-// one-launch forward, gemm_fwd1_kernel, takes it the same way.)
+// reads the snapshot instead (ticket == null) and fixed blocks, with
+// no tile of their own, apply to the live shadow concurrently — no
+// atomics at all. The ticket stays for shapes whose fwd GEMM takes no
+// snapshot. (The one-launch forward, gemm_fwd1_kernel, takes it the
+// same way.)
 // Unlike the rejected split-K last-arriver epilogue, the ticket's last
 // arriver reads NOTHING another block wrote in this launch — no stripe
 // pull, no acquire of foreign data, no L1-staleness hazard; the ticket
@@ -1259,27 +1277,71 @@ struct HeadTail {
   int C;
 };
 
-// SNAP (APPLY only): w2/b2 are the snapshot and the classifier block is
-// fixed, known at entry — it fetches its W2/b2 masters with everything
-// else. !SNAP: the ticket decides, so they are fetched after it.
-template <bool APPLY, bool GF32, bool SNAP>
-__global__ __launch_bounds__(256)
-void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
-                          void* __restrict__ Cout,
-                          void* __restrict__ colsum_out,
-                          int M, int N, int K, SmallSgd sg) {
-  __shared__ __align__(16) __bf16 hs[HB * HP];       // [row][k], all waves
-  __shared__ __align__(16) __bf16 wtp[4][CP * HP];   // per wave [c][k]
-  __shared__ __align__(16) __bf16 wpd[4][32 * CP];   // per wave, N tile rows
-  __shared__ __align__(16) __bf16 dls[HB * CP];      // [row][c]
-  __shared__ float ls[HB * LSP];
-  __shared__ float lsum[HB];
-  __shared__ __align__(16) __bf16 As[4][32 * BK];
-  __shared__ __align__(16) __bf16 Bs[4][32 * BK];
-  __shared__ float red[4][64 * 16];
-  __shared__ float csred[4][32];
-  __shared__ float db2p[CP * 16];
-  __shared__ unsigned tick;
+// Block roles. Everything but the ticket instantiation runs on a grid
+// two rows of blockIdx.x longer than the mt x nt dW1 tiles, and every
+// block has exactly ONE role, decided from its index alone (scalar
+// branches at the top of the kernel, one straight-line body per role):
+//   HT_TILE  x <  mt       a dW1 tile: h, classifier, logits, softmax,
+//                          dh, the two dW1 MFMAs, the W1 apply / dW1
+//                          store. No colsum, no bias, no classifier work.
+//   HT_DB1   x == mt       one per N tile: the same head into Bs, the
+//                          db1 colsum, the b1 apply / db1 store. No x,
+//                          no As, no dW1 MFMA, no red, no W1 master.
+//   HT_CLS   x == mt + 1   y == 0: dW2; y == 1: db2 and the loss (one
+//                          N tile: y == 0 does both; y >= 2 leaves at
+//                          once). h, logits, softmax into dls / lsum —
+//                          no x, wpd, dh, Bs, dW1.
+//   HT_ALL   the ticket instantiation, on the mt x nt grid: whoever
+//            arrives last must hold hs and dls, so every block is a
+//            tile, blockIdx.x == 0 adds db1 and the last arrival adds
+//            the classifier work.
+// Before, the snapshot step's last M tile ran the classifier work
+// behind its tile and the first M tile the colsum behind its own: the
+// kernel lasts as long as its longest block. SNAP tile blocks read only
+// the snapshot images, the HT_CLS blocks alone write live W2/b2 and the
+// HT_DB1 blocks alone b1; nothing else in the launch reads them.
+enum { HT_ALL = 0, HT_TILE = 1, HT_DB1 = 2, HT_CLS = 3 };
+
+struct HeadTailSmem {
+  alignas(16) __bf16 hs[HB * HP];       // [row][k], all waves
+  alignas(16) __bf16 wtp[4][(CP + 1) * HP];   // per wave [c][k] + a zero row
+  alignas(16) __bf16 wpd[4][32 * CP];   // per wave, N tile rows
+  alignas(16) __bf16 dls[HB * CP];      // [row][c]
+  float ls[HB * LSP];
+  float lsum[HB];
+  alignas(16) __bf16 As[4][32 * BK];
+  alignas(16) __bf16 Bs[4][32 * BK];
+  float red[4][64 * 16];
+  float csred[4][32];
+  float db2p[CP * 16];
+  unsigned tick;
+};
+
+// SNAP (APPLY only): w2/b2 are the snapshot and the classifier blocks
+// are fixed, known at entry — they fetch their W2/b2 masters with
+// everything else. !SNAP: the ticket decides, so they are fetched after
+// it. bx: the block's M tile (HT_ALL, HT_TILE); tiles: mt * nt.
+template <bool APPLY, bool GF32, bool SNAP, int ROLE>
+DEVINL void head_tail_body(HeadTailSmem& sm, const __bf16* __restrict__ X,
+                           const HeadTail& ht, void* __restrict__ Cout,
+                           void* __restrict__ colsum_out, int M, int N,
+                           int K, const SmallSgd& sg, int tiles) {
+  static_assert(ROLE != HT_ALL || (APPLY && !SNAP), "HT_ALL: ticket only");
+  static_assert(ROLE == HT_ALL || !APPLY || SNAP, "roles need no ticket");
+  constexpr bool TILE = ROLE == HT_ALL || ROLE == HT_TILE;  // x, As, dW1
+  constexpr bool DH = ROLE != HT_CLS;                       // wpd, dh, Bs
+  auto& hs = sm.hs;
+  auto& wtp = sm.wtp;
+  auto& wpd = sm.wpd;
+  auto& dls = sm.dls;
+  auto& ls = sm.ls;
+  auto& lsum = sm.lsum;
+  auto& As = sm.As;
+  auto& Bs = sm.Bs;
+  auto& red = sm.red;
+  auto& csred = sm.csred;
+  auto& db2p = sm.db2p;
+  auto& tick = sm.tick;
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int w = t >> 6;
@@ -1320,7 +1382,7 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
   // registers on the vector path put counted waits there, for loads
   // the compiler must assume pending on them.
   unsigned xs[16];
-  {
+  if (TILE) {
     const brsrc_t xr = buf_rsrc(X, K * M * 2);
     const int xrow = gk * M + gm;
     if (xvec) {
@@ -1359,7 +1421,7 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
       wkm[j] = *(const bf16x8*)&ht.w2[kSnapKmajOff + (q >> 4) * HP +
                                       (q & 15) * 8];
     }
-    wrow = *(const bf16x8*)&ht.w2[kSnapRowOff + n0 * CP + lane * 8];
+    if (DH) wrow = *(const bf16x8*)&ht.w2[kSnapRowOff + n0 * CP + lane * 8];
   } else {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -1375,15 +1437,15 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
   // high register was reused at once, behind a vmcnt(0)
   const int label = (int)__builtin_amdgcn_raw_buffer_load_b32(
       buf_rsrc(ht.labels, K * 8), (ks + kk) * 8, 0, 0);
+  // each role fetches the masters it applies, and no others
   SmallSgdPre pre = {};
   float pm2[16] = {};
   float pm2bv = 0.f;
-  // the block that applies W2/b2 where it is fixed (see below)
-  const bool snap_head =
-      APPLY && SNAP && blockIdx.x == gridDim.x - 1 && blockIdx.y == 0;
   if (APPLY) {
-    small_sgd_fetch_buf(sg, pre, m0, n0, M, N, w, lane);
-    if (snap_head) {
+    if (TILE) small_sgd_fetch_buf_w(sg, pre, m0, n0, M, N, w, lane);
+    if (ROLE == HT_DB1 || (ROLE == HT_ALL && blockIdx.x == 0))
+      small_sgd_fetch_buf_b(sg, pre, n0, N, lane);
+    if (ROLE == HT_CLS) {
       const brsrc_t w2r = buf_rsrc(sg.pm2w, N * C * 4);
       const int cb = kk < C ? kk * 4 : BUF_OOB;
 #pragma unroll
@@ -1402,8 +1464,10 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
       for (int c = 0; c < CP; ++c)
         if (!(lane + q * 64 < N && c < C)) wv[q][c] = (__bf16)0.f;
   }
-  const float bc = __builtin_bit_cast(float, braw << 16);   // 0 beyond C
-  if (!xvec) {
+  // beyond C: the pad bias (the load returned 0 there)
+  const float bc =
+      kk < C ? __builtin_bit_cast(float, braw << 16) : head_pad_bias();
+  if (TILE && !xvec) {
     u32x4 d0, d1;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1417,18 +1481,21 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
   if (!SNAP) {
     const bf16x8 z8 = {};
     for (int i = lane * 8; i < CP * HP; i += 64 * 8) *(bf16x8*)&wtw[i] = z8;
-    *(bf16x8*)&wpw[lane * 8] = z8;
+    if (DH) *(bf16x8*)&wpw[lane * 8] = z8;
   }
 #pragma unroll
   for (int i = 0; i < 16; ++i)
     *(bf16x4*)&hs[(ks + 2 * i + half) * HP + hc4] = hv[i];
+  // the zero row behind the CP class rows: the B fragment of the lanes
+  // of classes 16..31 (its HB live k)
+  if (lane < HB / 8) *(bf16x8*)&wtw[CP * HP + lane * 8] = bf16x8{};
   if (SNAP) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int q = lane + j * 64;
       *(bf16x8*)&wtw[(q >> 4) * HP + (q & 15) * 8] = wkm[j];
     }
-    *(bf16x8*)&wpw[lane * 8] = wrow;
+    if (DH) *(bf16x8*)&wpw[lane * 8] = wrow;
   } else {
     // wtw: column hr of the [c][k] image, all CP classes (wv is zero
     // beyond C and H — the same zeros the clear put there); wpw: the
@@ -1438,7 +1505,7 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
       const int hr = lane + q * 64;
 #pragma unroll
       for (int c = 0; c < CP; ++c) wtw[c * HP + hr] = wv[q][c];
-      if (hr >= n0 && hr < n0 + 32 && hr < N) {
+      if (DH && hr >= n0 && hr < n0 + 32 && hr < N) {
         bf16x8 lo, hi;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
@@ -1454,21 +1521,23 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
   // 3. logits for rows ks..ks+31 (the wave's DS pipe is in order, so
   // the fragment reads see the stores above without a barrier)
   {
-    const f32x16v acc = head_logits_tile(
-        &hs[(ks + kk) * HP], kk < CP ? &wtw[kk * HP] : nullptr, lane);
+    const f32x16v acc = head_logits_tile_all(
+        &hs[(ks + kk) * HP], &wtw[min(kk, CP) * HP], lane);
     head_store_logits(ls, acc, ks, bc, lane);
   }
   // 4. softmax + dlogits, one lane per row; rows >= B stay zero
   if (lane < 32) {
     const int row = ks + lane;
-    const bf16x8 z8 = {};
-    *(bf16x8*)&dls[row * CP] = z8;
-    *(bf16x8*)&dls[row * CP + 8] = z8;
     float neglogp = 0.f;
-    if (row < K)
-      neglogp = head_softmax_row(
-          &ls[row * LSP], C, label, ht.scale,
-          [&](int c, float d) { dls[row * CP + c] = (__bf16)d; });
+    if (row < K) {
+      neglogp = head_softmax_row_all(&ls[row * LSP], &dls[row * CP], C, label,
+                                     ht.scale);
+    } else {
+      // their logits are the bias, not zero
+      const bf16x8 z8 = {};
+      *(bf16x8*)&dls[row * CP] = z8;
+      *(bf16x8*)&dls[row * CP + 8] = z8;
+    }
     lsum[row] = neglogp;
   }
   // 5. dh fragment -> relu mask -> bf16 -> the k-major Bs image, where
@@ -1476,7 +1545,7 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
   // The 16 mask values do not depend on the MFMA: they are read ahead
   // of it, in one batch (read inside the loop, each one waited for the
   // Bs store before it, which might alias it — 16 LDS round trips)
-  {
+  if (DH) {
     const int colh = n0 + kk;
     __bf16 hm[16];
 #pragma unroll
@@ -1485,21 +1554,30 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
     const f32x16v acc =
         head_dh_tile(&dls[(ks + kk) * CP], &wpw[kk * CP], lane);
     wait_lgkm0();   // hm, under the MFMA: no LDS wait inside the loop
+    // h > 0 alone is the mask: beyond B and H the hs image holds the
+    // zeros the buffer loads returned. Row rl = 8 * (v >> 2) + 4 * half
+    // + (v & 3) of the image has swizzle term (rl >> 2) & 3 = (2 * (v >>
+    // 2) + half) & 3, two values per lane: two bases plus constants
+    // address the lane's 16 stores (sptr(Bw, rl, kk), spelled out)
+    const int sw = (kk >> 3) ^ half;
+    __bf16* const bq[2] = {Bw + half * 4 * BK + (sw << 3) + (kk & 7),
+                           Bw + half * 4 * BK + ((sw ^ 2) << 3) + (kk & 7)};
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const int rl = head_frag_row(v, lane);
-      const float hval = (float)hm[v];
-      const float m =
-          (ks + rl < K && colh < N && hval > 0.f) ? acc[v] : 0.f;
+      const float m = (float)hm[v] > 0.f ? acc[v] : 0.f;
       const bf16_t r = f2bf(m);
-      *sptr(Bw, rl, kk) = *(const __bf16*)&r;
+      bq[(v >> 2) & 1][((v >> 2) * 8 + (v & 3)) * BK] = *(const __bf16*)&r;
     }
   }
-  *(bf16x8*)sptr(Aw, kk, half * 16) = ra0;
-  *(bf16x8*)sptr(Aw, kk, half * 16 + 8) = ra1;
+  if (TILE) {
+    *(bf16x8*)sptr(Aw, kk, half * 16) = ra0;
+    *(bf16x8*)sptr(Aw, kk, half * 16 + 8) = ra1;
+  }
   // 6. db1 colsum from the bf16 dh values, same partials and tree as
-  // gemm_small's commit()/small_cs_reduce
-  if (blockIdx.x == 0) {
+  // gemm_small's commit()/small_cs_reduce (grads mode below 32 tiles
+  // sums serially after the barrier instead, see there)
+  if (ROLE == HT_DB1 ? (APPLY || tiles >= 32)
+                     : (ROLE == HT_ALL && blockIdx.x == 0)) {
     const bf16x8 rb0 = *(const bf16x8*)sptr(Bw, kk, half * 16);
     const bf16x8 rb1 = *(const bf16x8*)sptr(Bw, kk, half * 16 + 8);
     float csp[16] = {};
@@ -1511,63 +1589,57 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
     small_cs_reduce(csp, csred[w], lane);
   }
   // 7. dW1 partial of this wave's K span
-  f32x4 acc[4] = {};
-  if (ks < ke) {
+  if (TILE) {
+    f32x4 acc[4] = {};
+    if (ks < ke) {
 #pragma unroll
-    for (int kh = 0; kh < 2; ++kh) {
-      const int ko = kh * 16 + ((lane >> 5) << 3);
-      bf16x8 a = trs_frag(Aw, ko, lane);
-      bf16x8 b = trs_frag(Bw, ko, lane);
-      *(f32x16*)acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          a, b, *(f32x16*)acc, 0, 0, 0);
+      for (int kh = 0; kh < 2; ++kh) {
+        const int ko = kh * 16 + ((lane >> 5) << 3);
+        bf16x8 a = trs_frag(Aw, ko, lane);
+        bf16x8 b = trs_frag(Bw, ko, lane);
+        *(f32x16*)acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            a, b, *(f32x16*)acc, 0, 0, 0);
+      }
     }
-  }
 #pragma unroll
-  for (int v = 0; v < 16; ++v) red[w][lane * 16 + v] = ((float*)acc)[v];
+    for (int v = 0; v < 16; ++v) red[w][lane * 16 + v] = ((float*)acc)[v];
+  }
   __syncthreads();
   wait_vm0();   // the prefetched masters landed a whole head ago
 
-  bool head_block;
-  constexpr bool ticketed = APPLY && !SNAP;   // ht.ticket != null
-  if (APPLY) {
-    if (ticketed && t == 0)
+  constexpr bool ticketed = ROLE == HT_ALL;   // ht.ticket != null
+  if (ROLE == HT_ALL) {
+    if (t == 0)
       tick = __hip_atomic_fetch_add(ht.ticket, 1u, __ATOMIC_ACQ_REL,
                                     __HIP_MEMORY_SCOPE_AGENT);
     small_sgd_commit(sg, pre, red, csred, true, m0, n0, M, N, N, w, lane);
-    if (ticketed) {
-      __syncthreads();
-      head_block = tick == gridDim.x * gridDim.y - 1;
-      if (head_block) {
-        // only now known: the W2/b2 masters, all 17 loads in one batch
-        // (the stores above are to W1/b1, but may alias for all the
-        // compiler knows — the batch waits for them once, not per load)
+    __syncthreads();
+    if (tick != gridDim.x * gridDim.y - 1) return;
+    // only now known: the W2/b2 masters, all 17 loads in one batch
+    // (the stores above are to W1/b1, but may alias for all the
+    // compiler knows — the batch waits for them once, not per load)
 #pragma unroll
-        for (int v = 0; v < 16; ++v) {
-          const int hrow = ks + head_frag_row(v, lane);
-          pm2[v] = sg.pm2w[(kk < C && hrow < N) ? hrow * C + kk : 0];
-        }
-        pm2bv = sg.pm2b[t < C ? t : 0];
-        wait_vm0();
-      }
-    } else {
-      // w2/b2 are a snapshot the preceding launch took: nobody reads
-      // the live shadow here, so a fixed block applies right away, in
-      // parallel with the other tiles (the ragged last M tile has the
-      // least W1 work and no b1 apply); its masters came with step 1
-      head_block = snap_head;
+    for (int v = 0; v < 16; ++v) {
+      const int hrow = ks + head_frag_row(v, lane);
+      pm2[v] = sg.pm2w[(kk < C && hrow < N) ? hrow * C + kk : 0];
     }
-  } else {
-    if (gridDim.x * gridDim.y >= 32) {
+    pm2bv = sg.pm2b[t < C ? t : 0];
+    wait_vm0();
+  } else if (ROLE == HT_TILE) {
+    if (APPLY) {
+      small_sgd_commit(sg, pre, red, csred, false, m0, n0, M, N, N, w, lane);
+    } else if (tiles >= 32) {
       if (w == 0)
-        small_store(red, csred, true, nullptr, false, Cout, GF32, 0,
-                    colsum_out, GF32, m0, n0, M, N, N, lane);
+        small_store(red, csred, false, nullptr, false, Cout, GF32, 0,
+                    nullptr, GF32, m0, n0, M, N, N, lane);
     } else {
       // below 32 tiles gemm_bias_act runs dW1 on gemm_kernel<tn,CS>,
       // not on gemm_small_kernel: K chained through ONE 16x16x32
-      // accumulator per element and a serial colsum over k. Reproduce
-      // that order from the four waves' k-major images (all complete
-      // after the barrier) so grads mode equals the two-kernel path
-      // bit for bit at every tile count. Wave w owns one 16x16 quarter.
+      // accumulator per element and a serial colsum over k (the HT_DB1
+      // blocks, below). Reproduce that order from the four waves'
+      // k-major images (all complete after the barrier) so grads mode
+      // equals the two-kernel path bit for bit at every tile count.
+      // Wave w owns one 16x16 quarter.
       const int wr = w >> 1, wc = w & 1;
       const int kfrag = (lane >> 4) * 8;
       const int kr = kfrag + ((lane & 15) >> 2);
@@ -1595,22 +1667,31 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
           else ((__bf16*)Cout)[(long)row * N + col] = (__bf16)v;
         }
       }
-      if (blockIdx.x == 0 && t < 32 && n0 + t < N) {
-        float cs = 0.f;
-        for (int q = 0; q * 32 < K; ++q)
-#pragma unroll
-          for (int k2 = 0; k2 < 32; ++k2) cs += (float)*sptr(Bs[q], k2, t);
-        if (GF32) ((float*)colsum_out)[n0 + t] = cs;
-        else ((__bf16*)colsum_out)[n0 + t] = (__bf16)cs;
-      }
     }
-    head_block = blockIdx.x == 0 && blockIdx.y == 0;
+    return;
+  } else if (ROLE == HT_DB1) {
+    if (APPLY) {
+      if (t < 32) small_sgd_commit_b(sg, pre, csred, n0, N, t);
+    } else if (tiles >= 32) {
+      if (t < 32) small_store_cs(csred, colsum_out, GF32, n0, N, t);
+    } else if (t < 32 && n0 + t < N) {
+      float cs = 0.f;
+      for (int q = 0; q * 32 < K; ++q)
+#pragma unroll
+        for (int k2 = 0; k2 < 32; ++k2) cs += (float)*sptr(Bs[q], k2, t);
+      if (GF32) ((float*)colsum_out)[n0 + t] = cs;
+      else ((__bf16*)colsum_out)[n0 + t] = (__bf16)cs;
+    }
+    return;
   }
-  if (!head_block) return;
+  // HT_CLS: with two N tiles or more, y == 0 forms dW2 and y == 1 db2
+  // and the loss, side by side; both hold the same hs and dls
+  const bool do_dw2 = ROLE == HT_ALL || gridDim.y < 2 || blockIdx.y == 0;
+  const bool do_db2 = ROLE == HT_ALL || gridDim.y < 2 || blockIdx.y == 1;
 
   // 8. classifier grads by ONE block: dW2[H,C] = h^T @ dls, K = B over
   // the eight 16-row steps, wave w owns hidden rows 32w..32w+31
-  {
+  if (do_dw2) {
     f32x16v acc2 = {};
     const int kr = (lane & 15) >> 2;
     const int ca = ks + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
@@ -1648,6 +1729,7 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
       }
     }
   }
+  if (!do_db2) return;
   // db2[c] = sum_b dls[b][c], 16 partial lanes per class as in the head
   if (t < C * 16) {
     const int c = t >> 4, part = t & 15;
@@ -1681,6 +1763,33 @@ void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
   if (ticketed && t == 0)
     __hip_atomic_store(ht.ticket, 0u, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One role per block, chosen by scalar compares of the block index
+// (roles and grid: see HT_TILE above; launch_mlp_head_tail sizes it).
+template <bool APPLY, bool GF32, bool SNAP>
+__global__ __launch_bounds__(256)
+void mlp_head_tail_kernel(const __bf16* __restrict__ X, HeadTail ht,
+                          void* __restrict__ Cout,
+                          void* __restrict__ colsum_out,
+                          int M, int N, int K, SmallSgd sg) {
+  __shared__ HeadTailSmem sm;
+  if constexpr (APPLY && !SNAP) {
+    head_tail_body<APPLY, GF32, SNAP, HT_ALL>(
+        sm, X, ht, Cout, colsum_out, M, N, K, sg, gridDim.x * gridDim.y);
+  } else {
+    const int mt = gridDim.x - 2;
+    const int tiles = mt * gridDim.y;
+    if ((int)blockIdx.x < mt)
+      head_tail_body<APPLY, GF32, SNAP, HT_TILE>(
+          sm, X, ht, Cout, colsum_out, M, N, K, sg, tiles);
+    else if ((int)blockIdx.x == mt)
+      head_tail_body<APPLY, GF32, SNAP, HT_DB1>(
+          sm, X, ht, Cout, colsum_out, M, N, K, sg, tiles);
+    else if (blockIdx.y < 2)
+      head_tail_body<APPLY, GF32, SNAP, HT_CLS>(
+          sm, X, ht, Cout, colsum_out, M, N, K, sg, tiles);
+  }
 }
 
 // split-K phase 2 fused with the SGD apply (the NMF factor update):
@@ -1954,7 +2063,10 @@ void launch_mlp_head_tail(const bf16_t* x, const HeadTailArgs* hta,
                           void* dw1, void* db1, bool grads_f32, int M,
                           int H, int B, const SmallSgdArgs* sga,
                           hipStream_t stream) {
-  dim3 grid(ceil_div(M, 32), ceil_div(H, 32)), block(256);
+  // two more rows of blockIdx.x for the db1 and classifier roles; the
+  // ticket instantiation runs on the tiles alone
+  const bool roles = !(sga && hta->ticket != nullptr);
+  dim3 grid(ceil_div(M, 32) + (roles ? 2 : 0), ceil_div(H, 32)), block(256);
   HeadTail ht;
   ht.h = (const __bf16*)hta->h;
   ht.w2 = (const __bf16*)hta->w2;

@@ -99,6 +99,82 @@ DEVINL float head_softmax_row(const float* lr, int C, int label,
   return hit ? -__logf(fmaxf(pl, 1e-30f)) : 0.f;
 }
 
+// The two phases above without runtime generality, for the fused
+// head+tail kernel alone (mlp_head_mfma_kernel keeps the forms above:
+// it is the route the exact tests compare against). Same operations on
+// the same values in the same order — the pad classes C..CP-1 take part
+// as exact zeros instead of being predicated away.
+
+// head_logits_tile with a B fragment for EVERY lane: brow is the lane's
+// w^T row, or an all-zero row for the classes beyond the padded image.
+// All 16 fragment reads are issued ahead of the first MFMA (the guarded
+// form was eight LDS round trips in a row).
+DEVINL f32x16v head_logits_tile_all(const __bf16* arow, const __bf16* brow,
+                                    int lane) {
+  bf16x8 a[HB / 16], bv[HB / 16];
+#pragma unroll
+  for (int kh = 0; kh < HB / 16; ++kh) {
+    const int k0 = kh * 16 + ((lane >> 5) << 3);
+    a[kh] = *(const bf16x8*)&arow[k0];
+    bv[kh] = *(const bf16x8*)&brow[k0];
+  }
+  f32x16v acc = {};
+#pragma unroll
+  for (int kh = 0; kh < HB / 16; ++kh)
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kh], bv[kh], acc, 0, 0, 0);
+  return acc;
+}
+
+// The bias a pad class is staged with: its logit is 0 + bias (the
+// classifier columns are zero there), cannot win the max and has
+// exp(l - max) == +0 exactly, so sum, p and d come out as if the class
+// had been skipped: sum + 0 is exact and p = d = +0 is what the zero
+// fill stored.
+DEVINL float head_pad_bias() { return -__builtin_inff(); }
+
+// head_softmax_row over all CP slots of a row staged with
+// head_pad_bias: no class predicate. d of the whole row goes out as two
+// b128 stores to drow (the row's CP dlogits), then the label's element
+// is patched by one b16 store behind them (same wave, in-order DS
+// pipe). e[label] is recomputed from one more read of l[label] — the
+// same exp of the same difference, the same bits. The parent's
+// (p - onehot) * scale compiles to fma(e, inv, -onehot) then a multiply
+// and p[label] to a plain multiply; both are spelled out here so that
+// contraction cannot decide otherwise. With onehot == 0 the fma is the
+// rounded product itself.
+DEVINL float head_softmax_row_all(const float* lr, __bf16* drow, int C,
+                                  int label, float scale) {
+  float l[CP];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) l[c] = lr[c];
+  const bool hit = (unsigned)label < (unsigned)C;
+  const int lab = hit ? label : 0;
+  const float ll = lr[lab];
+  float mx = -3.4e38f;
+#pragma unroll
+  for (int c = 0; c < CP; ++c) mx = fmaxf(mx, l[c]);
+  float sum = 0.f;
+  float e[CP];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    e[c] = __expf(l[c] - mx);
+    sum += e[c];
+  }
+  const float inv = 1.f / sum;
+  bf16x8 lo, hi;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    lo[c] = (__bf16)((e[c] * inv) * scale);
+    hi[c] = (__bf16)((e[8 + c] * inv) * scale);
+  }
+  *(bf16x8*)&drow[0] = lo;
+  *(bf16x8*)&drow[8] = hi;
+  const float el = __expf(ll - mx);
+  if (hit) drow[lab] = (__bf16)(__builtin_fmaf(el, inv, -1.f) * scale);
+  const float pl = el * inv;
+  return hit ? -__logf(fmaxf(pl, 1e-30f)) : 0.f;
+}
+
 // dh tile [32 rows, 32 hidden cols] = dls rows @ w^T, K = CP (one
 // MFMA). drow: this lane's dls row; wrow: this lane's wpad row (hidden
 // column lane & 31 of the tile). Unmasked — the caller applies h > 0.

@@ -5,6 +5,13 @@ Usage: python tools/kinstr.py <file.s> <kernel-name substring> [...]
 For every kernel whose symbol contains the substring: the instruction
 count, its split by class (from the mnemonic's prefix alone) and the
 same split for the part before the first s_barrier.
+
+       python tools/kinstr.py --blocks <file.s> <kernel-name substring>
+
+The kernel's basic blocks instead: first instruction, label, count and
+the branch (with its target) or barrier that ends each. A kernel that
+dispatches on the block index has one barrier per role; the executed
+length of a role is the sum of the blocks on its path.
 """
 import re
 import sys
@@ -39,8 +46,10 @@ def classify(m):
     return "other"
 
 
-def kernels(path):
-    """(symbol, [mnemonic, ...]) of every function body in the file."""
+def kernels(path, labels=False):
+    """(symbol, [mnemonic, ...]) of every function body in the file.
+    labels: local labels (.LBB...) stay in the list as "label:" and a
+    branch keeps its target ("s_cbranch_scc1 .LBB7_12")."""
     name, body = None, []
     label = re.compile(r"^([A-Za-z_.$][\w.$]*):")
     for line in open(path):
@@ -51,6 +60,8 @@ def kernels(path):
         if m:
             if not m.group(1).startswith(".") and name is None:
                 name, body = m.group(1), []
+            elif labels and name is not None:
+                body.append(m.group(1) + ":")
             continue
         s = line.strip()
         if s.startswith(".") or name is None:
@@ -59,9 +70,38 @@ def kernels(path):
                     yield name, body
                 name, body = None, []
             continue
-        body.append(s.split()[0])
+        f = s.split()
+        body.append(" ".join(f[:2]) if labels and is_branch(f[0]) else f[0])
     if name is not None and body:
         yield name, body
+
+
+def is_branch(m):
+    return m.startswith(("s_cbranch", "s_branch", "s_setpc", "s_swappc",
+                         "s_endpgm"))
+
+
+def blocks(mn):
+    """Basic blocks of a labelled body (kernels(..., labels=True)):
+    (index of the first instruction, label or "", instruction count,
+    terminating branch with its target, or "" when it falls through).
+    A barrier ends a block as well, so the counts on either side of it
+    can be added up along a path read off the branch targets."""
+    out, n, first, lab, cnt = [], 0, 0, "", 0
+    for m in mn:
+        if m.endswith(":"):
+            if cnt:
+                out.append((first, lab, cnt, ""))
+            first, lab, cnt = n, m[:-1], 0
+            continue
+        n += 1
+        cnt += 1
+        if is_branch(m.split()[0]) or m.startswith("s_barrier"):
+            out.append((first, lab, cnt, m))
+            first, lab, cnt = n, "", 0
+    if cnt:
+        out.append((first, lab, cnt, ""))
+    return out
 
 
 def table(mn):
@@ -72,7 +112,17 @@ def table(mn):
 
 
 def main():
-    path, subs = sys.argv[1], sys.argv[2:]
+    args = [a for a in sys.argv[1:] if a != "--blocks"]
+    path, subs = args[0], args[1:]
+    if "--blocks" in sys.argv:
+        for name, mn in kernels(path, labels=True):
+            if not any(s in name for s in subs):
+                continue
+            print(name)
+            print("  %6s %-12s %6s  %s" % ("first", "label", "count", "ends"))
+            for first, lab, cnt, end in blocks(mn):
+                print("  %6d %-12s %6d  %s" % (first, lab, cnt, end))
+        return
     for name, mn in kernels(path):
         if not any(s in name for s in subs):
             continue
