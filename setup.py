@@ -31,6 +31,7 @@ sources = [
     os.path.join(CSRC, "coalesce.hip"),
     os.path.join(CSRC, "hash.hip"),
     os.path.join(CSRC, "elementwise.hip"),
+    os.path.join(CSRC, "interaction.hip"),
 ]
 
 setup(

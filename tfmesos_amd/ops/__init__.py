@@ -26,6 +26,9 @@ stamps), hash_compact (keep the flagged rows, dense again), hash_remove.
 Feature admission: HashAdmission (a count-min sketch), hash_admit_cells,
 hash_find_or_admit, and the serving ops that read an absent key's initial
 row instead of storing it: hash_gather_init, hash_embedding_bag.
+What a CTR model does with the pooled rows next: dot_interaction, the fused
+pairwise feature interaction (DLRM's dot interaction / an FM's Gram matrix),
+forward and backward.
 """
 
 import collections
@@ -507,6 +510,94 @@ def embedding_bag(table, ids, offsets, weights=None, combiner="sum",
     out = torch.zeros(offsets.numel() - 1, table.shape[1])
     out.index_add_(0, bag_of[keep], c[keep, None] * rows)
     return out.to(out_dtype)
+
+
+# -------------------------------------------- pairwise feature interaction
+
+DOT_INTERACTION_MAX_F = 64      # csrc/interaction.h: kDotMaxF
+
+
+def _dot_pairs(F, diagonal, dev):
+    return torch.tril_indices(F, F, 0 if diagonal else -1, device=dev)
+
+
+class _DotInteractionFn(torch.autograd.Function):
+    """Differentiable dot_interaction. GPU: csrc/interaction.hip, one
+    kernel each way; CPU (and the shapes with nothing to launch: B == 0,
+    no pairs): the same op in plain fp32 torch."""
+
+    @staticmethod
+    def forward(ctx, x, diagonal, keep_first, out_dtype):
+        ctx.save_for_backward(x)
+        ctx.flags = (diagonal, keep_first)
+        B, F, D = x.shape
+        i, j = _dot_pairs(F, diagonal, x.device)
+        ctx.launch = x.is_cuda and B > 0 and D > 0 and i.numel() > 0
+        if ctx.launch:
+            return _ext().dot_interaction_fwd(
+                x, diagonal, keep_first, out_dtype == torch.float32)
+        xf = x.float()
+        out = torch.bmm(xf, xf.transpose(1, 2))[:, i, j]
+        if keep_first:
+            out = torch.cat([xf[:, 0], out], 1)
+        return out.to(out_dtype)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, = ctx.saved_tensors
+        diagonal, keep_first = ctx.flags
+        dout = dout.contiguous()
+        if ctx.launch:
+            return (_ext().dot_interaction_bwd(x, dout, diagonal, keep_first),
+                    None, None, None)
+        B, F, D = x.shape
+        i, j = _dot_pairs(F, diagonal, x.device)
+        g = dout.float()
+        low = torch.zeros(B, F, F, device=x.device)
+        low[:, i, j] = g[:, D if keep_first else 0:]
+        dx = torch.bmm(low + low.transpose(1, 2), x.float())
+        if keep_first:
+            dx[:, 0] += g[:, :D]
+        return dx.to(x.dtype), None, None, None
+
+
+def dot_interaction(x, diagonal=False, keep_first=True, out_dtype=None):
+    """Pairwise feature interaction (DLRM's "dot" interaction; the Gram
+    matrix under a factorization machine's second-order term).
+
+    x is bf16 [B, F, D]: F feature vectors per example, e.g. the
+    ``torch.stack(..., 1)`` of F pooled pulls (in DLRM feature 0 is the
+    bottom MLP's output). Z[b] = x[b] @ x[b]^T is accumulated in fp32 and
+    its pairs (i, j), j < i (j <= i with ``diagonal``), are written in the
+    row-major order of ``torch.tril_indices``: P = F(F-1)/2 or F(F+1)/2
+    values per example. The result is [B, P], or with ``keep_first``
+    [B, D + P] whose first D columns are x[:, 0, :] itself (DLRM's cat).
+    Values are rounded once from fp32 (round to nearest even) to
+    ``out_dtype``: torch.bfloat16 (default) or torch.float32.
+
+    Differentiable in x: dx[b] = (L + L^T) x[b] with L the lower triangle
+    unpacked from dout[b] (so a diagonal entry counts twice), plus
+    dout[b, :D] on row 0 with ``keep_first``; fp32 accumulation, rounded
+    once to bf16. dout may be bf16 or fp32; on the GPU an fp32 dout is
+    rounded to bf16 on its way into the MFMA operand.
+    ``x.grad[:, f, :].contiguous()`` is the bag gradient to hand to
+    ``push_pooled`` of table f.
+
+    F <= 64 (DOT_INTERACTION_MAX_F, the kernel's tile limit); any D >= 1.
+    GPU: csrc/interaction.hip — no atomics, bit-reproducible, no host sync.
+    """
+    if x.dim() != 3 or x.dtype != torch.bfloat16:
+        raise ValueError("dot_interaction: x must be bf16 [B, F, D], got %s %s"
+                         % (x.dtype, tuple(x.shape)))
+    out_dtype = torch.bfloat16 if out_dtype is None else out_dtype
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("dot_interaction: out_dtype must be torch.bfloat16 "
+                         "or torch.float32")
+    if not 1 <= x.shape[1] <= DOT_INTERACTION_MAX_F:
+        raise ValueError("dot_interaction: F = %d, need 1 <= F <= %d"
+                         % (x.shape[1], DOT_INTERACTION_MAX_F))
+    return _DotInteractionFn.apply(x.contiguous(), bool(diagonal),
+                                   bool(keep_first), out_dtype)
 
 
 # ----------------------------------------------- row-sharded table routing

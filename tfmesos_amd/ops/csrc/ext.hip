@@ -11,6 +11,7 @@
 #include "conv.h"
 #include "elementwise.h"
 #include "gemm.h"
+#include "interaction.h"
 #include "pool.h"
 #include "softmax_xent.h"
 
@@ -783,6 +784,53 @@ torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor act) {
   return dx;
 }
 
+// Pairwise feature interaction (interaction.hip): x [B,F,D] bf16 ->
+// [B, (keep ? D : 0) + P], the kept row 0 then the packed lower triangle of
+// x[b] x[b]^T (P = F(F-1)/2, or F(F+1)/2 with diag), rounded once from fp32.
+static long dot_pairs(long F, bool diag) {
+  return diag ? F * (F + 1) / 2 : F * (F - 1) / 2;
+}
+
+static void dot_check_x(const char* op, const torch::Tensor& x, bool diag) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.is_contiguous() &&
+              x.scalar_type() == torch::kBFloat16,
+              op, ": x must be contiguous bf16 [B,F,D] on GPU");
+  TORCH_CHECK(x.size(0) > 0 && x.size(1) >= 1 && x.size(1) <= kDotMaxF &&
+              x.size(2) >= 1 && x.size(2) <= (long)INT_MAX / kDotMaxF &&
+              dot_pairs(x.size(1), diag) > 0,
+              op, ": need B > 0, 1 <= F <= ", kDotMaxF, ", D >= 1 and at least "
+              "one pair");
+}
+
+torch::Tensor dot_interaction_fwd(torch::Tensor x, bool diag, bool keep,
+                                  bool out_f32) {
+  dot_check_x("dot_interaction_fwd", x, diag);
+  const long B = x.size(0), F = x.size(1), D = x.size(2);
+  auto out = torch::empty(
+      {B, (keep ? D : 0) + dot_pairs(F, diag)},
+      x.options().dtype(out_f32 ? torch::kFloat32 : torch::kBFloat16));
+  launch_dot_interaction_fwd(x.data_ptr(), out.data_ptr(), !out_f32, B, (int)F,
+                             (int)D, diag, keep, cur_stream());
+  return out;
+}
+
+// dx [B,F,D] bf16 = (L + L^T) x[b], L unpacked from dout[b] (bf16 or fp32,
+// the forward's shape), plus dout[b,:D] on row 0 when keep.
+torch::Tensor dot_interaction_bwd(torch::Tensor x, torch::Tensor dout,
+                                  bool diag, bool keep) {
+  dot_check_x("dot_interaction_bwd", x, diag);
+  const long B = x.size(0), F = x.size(1), D = x.size(2);
+  TORCH_CHECK(dout.is_cuda() && dout.dim() == 2 && dout.size(0) == B &&
+              dout.size(1) == (keep ? D : 0) + dot_pairs(F, diag),
+              "dot_interaction_bwd: dout must be [B, (keep ? D : 0) + P]");
+  bool g_bf16;
+  const void* g = grad_ptr(dout, &g_bf16);
+  auto dx = torch::empty_like(x);
+  launch_dot_interaction_bwd(x.data_ptr(), g, g_bf16, dx.data_ptr(), B, (int)F,
+                             (int)D, diag, keep, cur_stream());
+  return dx;
+}
+
 torch::Tensor colsum(torch::Tensor x, torch::Tensor out) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
               x.is_contiguous() && x.dim() == 2, "colsum: bf16 [M,N]");
@@ -1511,4 +1559,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   bind_sparse(m);
   m.def("relu_bwd", &relu_bwd);
   m.def("colsum", &colsum, py::arg("x"), py::arg("out"));
+  m.def("dot_interaction_fwd", &dot_interaction_fwd, py::arg("x"),
+        py::arg("diag"), py::arg("keep"), py::arg("out_f32"));
+  m.def("dot_interaction_bwd", &dot_interaction_bwd, py::arg("x"),
+        py::arg("dout"), py::arg("diag"), py::arg("keep"));
 }
