@@ -32,6 +32,7 @@ sources = [
     os.path.join(CSRC, "hash.hip"),
     os.path.join(CSRC, "elementwise.hip"),
     os.path.join(CSRC, "interaction.hip"),
+    os.path.join(CSRC, "sampled_softmax.hip"),
 ]
 
 setup(

@@ -28,7 +28,9 @@ hash_find_or_admit, and the serving ops that read an absent key's initial
 row instead of storing it: hash_gather_init, hash_embedding_bag.
 What a CTR model does with the pooled rows next: dot_interaction, the fused
 pairwise feature interaction (DLRM's dot interaction / an FM's Gram matrix),
-forward and backward.
+forward and backward. What a model with a large output vocabulary trains
+against: sampled_softmax_loss, the fused candidate-sampling loss (TF's
+sampled_softmax_loss; in-batch negatives), forward and backward.
 """
 
 import collections
@@ -598,6 +600,130 @@ def dot_interaction(x, diagonal=False, keep_first=True, out_dtype=None):
                          % (x.shape[1], DOT_INTERACTION_MAX_F))
     return _DotInteractionFn.apply(x.contiguous(), bool(diagonal),
                                    bool(keep_first), out_dtype)
+
+
+# ------------------------------------------------------ sampled softmax loss
+
+SAMPLED_SOFTMAX_MAX_D = 256     # csrc/sampled_softmax.h: kSampledMaxD
+
+
+def _sampled_scores(h, w_true, w_samp, true_adj, samp_adj, labels, sampled):
+    """fp32 (t [B], l [B,S] with the accidental hits at -inf)."""
+    hf = h.float()
+    t = (hf * w_true.float()).sum(1)
+    l = hf @ w_samp.float().t()
+    if true_adj is not None:
+        t = t + true_adj
+    if samp_adj is not None:
+        l = l + samp_adj
+    if labels is not None:
+        l = l.masked_fill(labels[:, None] == sampled[None, :], float("-inf"))
+    return t, l
+
+
+class _SampledSoftmaxFn(torch.autograd.Function):
+    """Differentiable sampled_softmax_loss. GPU: csrc/sampled_softmax.hip,
+    one MFMA kernel each way (plus the forward's small finishing kernel);
+    CPU (and B == 0 or S == 0 on a device): the same op in plain fp32
+    torch."""
+
+    @staticmethod
+    def forward(ctx, h, w_true, w_samp, true_adj, samp_adj, labels, sampled):
+        ctx.launch = h.is_cuda and h.shape[0] > 0 and w_samp.shape[0] > 0
+        args = (h, w_true, w_samp, true_adj, samp_adj, labels, sampled)
+        if ctx.launch:
+            loss, lse = _ext().sampled_softmax_fwd(*args)
+        else:
+            t, l = _sampled_scores(*args)
+            lse = torch.logsumexp(torch.cat([t[:, None], l], 1), 1)
+            loss = lse - t
+        ctx.save_for_backward(*args, lse, loss)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (h, w_true, w_samp, true_adj, samp_adj, labels, sampled, lse,
+         loss) = ctx.saved_tensors
+        g = g.float().contiguous()
+        if ctx.launch:
+            dh, dwt, dws, dta, dsa = _ext().sampled_softmax_bwd(
+                h, w_true, w_samp, samp_adj, labels, sampled, lse, loss, g)
+        else:
+            _, l = _sampled_scores(h, w_true, w_samp, true_adj, samp_adj,
+                                   labels, sampled)
+            p = g[:, None] * torch.exp(l - lse[:, None])
+            dta = g * torch.expm1(-loss)
+            dsa = p.sum(0)
+            hf = h.float()
+            dh = (p @ w_samp.float() + dta[:, None] * w_true.float()).to(h.dtype)
+            dws = (p.t() @ hf).to(h.dtype)
+            dwt = (dta[:, None] * hf).to(h.dtype)
+        return (dh, dwt, dws, None if true_adj is None else dta,
+                None if samp_adj is None else dsa, None, None)
+
+
+def sampled_softmax_loss(h, w_true, w_samp, true_adj=None, samp_adj=None,
+                         labels=None, sampled=None):
+    """Softmax cross-entropy over each example's label and S sampled
+    candidates shared by the batch (TF's ``sampled_softmax_loss``; with the
+    batch's own items as candidates, the in-batch-negatives loss). For a
+    model whose output vocabulary is too large to form [B, V] logits: the
+    caller pulls the output-embedding rows of the labels and of the
+    candidates and passes them here.
+
+    h, w_true are bf16 [B, D] (w_true[b] is the pulled row of example b's
+    label), w_samp is bf16 [S, D]. true_adj [B] and samp_adj [S] are fp32
+    additive terms (the caller's ``bias - log Q``; None is 0). labels [B]
+    and sampled [S] are int64 ids, used only to drop accidental hits — the
+    pairs with sampled[s] == labels[b]; give both or neither.
+
+        t[b] = h[b].w_true[b] + true_adj[b]
+        l[b,s] = h[b].w_samp[s] + samp_adj[s]
+        loss[b] = log(exp t[b] + sum over kept s of exp l[b,s]) - t[b]
+
+    Returns loss, fp32 [B]; dot products, exp, log and sums are fp32,
+    max-subtracted. Differentiable in h, w_true, w_samp (bf16 gradients,
+    accumulated in fp32 and rounded once; on the GPU the probabilities are
+    rounded to bf16 on their way into the MFMA operand) and in the two
+    adjustments (fp32). Push ``cat(w_true.grad, w_samp.grad)`` with ids
+    ``cat(labels, sampled)``: the sparse applies sum duplicates. In-batch
+    negatives is ``(h, w, w, adj, adj, labels, labels)``: the diagonal is an
+    accidental hit and autograd adds the two gradients of w.
+
+    1 <= D <= 256 (SAMPLED_SOFTMAX_MAX_D), any B and S. No table, sampler
+    or Q here: pulling rows and choosing candidates stay with the caller.
+    GPU: csrc/sampled_softmax.hip — nothing [B, S]-sized in memory, no
+    atomics, bit-reproducible, no host sync.
+    """
+    name = "sampled_softmax_loss"
+    for t in (h, w_true, w_samp):
+        if t.dim() != 2 or t.dtype != torch.bfloat16:
+            raise ValueError("%s: h, w_true, w_samp must be bf16 matrices, "
+                             "got %s %s" % (name, t.dtype, tuple(t.shape)))
+    B, D = h.shape
+    S = w_samp.shape[0]
+    if w_true.shape != h.shape or w_samp.shape[1] != D:
+        raise ValueError("%s: need h, w_true [B, D] and w_samp [S, D], got "
+                         "%s %s %s" % (name, tuple(h.shape),
+                                       tuple(w_true.shape),
+                                       tuple(w_samp.shape)))
+    if not 1 <= D <= SAMPLED_SOFTMAX_MAX_D:
+        raise ValueError("%s: D = %d, need 1 <= D <= %d"
+                         % (name, D, SAMPLED_SOFTMAX_MAX_D))
+    for t, n, what in ((true_adj, B, "true_adj [B]"),
+                       (samp_adj, S, "samp_adj [S]")):
+        if t is not None and (t.dtype != torch.float32 or t.shape != (n,)):
+            raise ValueError("%s: %s must be fp32" % (name, what))
+    if (labels is None) != (sampled is None):
+        raise ValueError("%s: give both labels and sampled, or neither"
+                         % name)
+    for t, n, what in ((labels, B, "labels [B]"), (sampled, S, "sampled [S]")):
+        if t is not None and (t.dtype != torch.int64 or t.shape != (n,)):
+            raise ValueError("%s: %s must be int64" % (name, what))
+    c = lambda t: None if t is None else t.contiguous()  # noqa: E731
+    return _SampledSoftmaxFn.apply(h.contiguous(), w_true.contiguous(),
+                                   w_samp.contiguous(), c(true_adj),
+                                   c(samp_adj), c(labels), c(sampled))
 
 
 # ----------------------------------------------- row-sharded table routing

@@ -13,6 +13,7 @@
 #include "gemm.h"
 #include "interaction.h"
 #include "pool.h"
+#include "sampled_softmax.h"
 #include "softmax_xent.h"
 
 namespace {
@@ -831,6 +832,94 @@ torch::Tensor dot_interaction_bwd(torch::Tensor x, torch::Tensor dout,
   return dx;
 }
 
+// Sampled softmax loss (sampled_softmax.hip): h, w_true [B,D], w_samp [S,D]
+// bf16; the optional true_adj [B], samp_adj [S] fp32 and labels [B], sampled
+// [S] int64 (ids: both or neither).
+typedef c10::optional<torch::Tensor> OptTensor;
+
+static void ssm_check_rows(const char* op, const torch::Tensor& h,
+                           const torch::Tensor& w_true,
+                           const torch::Tensor& w_samp) {
+  for (const torch::Tensor* t : {&h, &w_true, &w_samp})
+    TORCH_CHECK(t->is_cuda() && t->dim() == 2 && t->is_contiguous() &&
+                t->scalar_type() == torch::kBFloat16,
+                op, ": h, w_true, w_samp must be contiguous bf16 matrices "
+                "on GPU");
+  TORCH_CHECK(h.size(0) >= 1 && h.size(0) <= INT_MAX - 64 &&
+              w_samp.size(0) >= 1 && w_samp.size(0) <= INT_MAX - 64 &&
+              h.size(1) >= 1 && h.size(1) <= kSampledMaxD &&
+              w_true.sizes() == h.sizes() && w_samp.size(1) == h.size(1),
+              op, ": need h, w_true [B,D], w_samp [S,D] with B, S >= 1 and "
+              "1 <= D <= ", kSampledMaxD);
+}
+
+static const float* ssm_f32(const char* op, const OptTensor& t, long n) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->dim() == 1 &&
+              t->size(0) == n && t->scalar_type() == torch::kFloat32,
+              op, ": an fp32 vector has the wrong dtype or length");
+  return t->data_ptr<float>();
+}
+
+static void ssm_ids(const char* op, const OptTensor& labels,
+                    const OptTensor& sampled, long B, long S,
+                    const long** lp, const long** sp) {
+  TORCH_CHECK(labels.has_value() == sampled.has_value(),
+              op, ": give both labels and sampled, or neither");
+  *lp = *sp = nullptr;
+  if (!labels.has_value()) return;
+  TORCH_CHECK(i64_vec(*labels) && labels->size(0) == B && i64_vec(*sampled) &&
+              sampled->size(0) == S,
+              op, ": labels [B] and sampled [S] must be int64 on GPU");
+  *lp = (const long*)labels->data_ptr<int64_t>();
+  *sp = (const long*)sampled->data_ptr<int64_t>();
+}
+
+// -> (loss [B], lse [B]) fp32
+std::tuple<torch::Tensor, torch::Tensor> sampled_softmax_fwd(
+    torch::Tensor h, torch::Tensor w_true, torch::Tensor w_samp,
+    OptTensor true_adj, OptTensor samp_adj, OptTensor labels,
+    OptTensor sampled) {
+  const char* op = "sampled_softmax_fwd";
+  ssm_check_rows(op, h, w_true, w_samp);
+  const long B = h.size(0), S = w_samp.size(0), D = h.size(1);
+  const long *lp, *sp;
+  ssm_ids(op, labels, sampled, B, S, &lp, &sp);
+  auto f32 = h.options().dtype(torch::kFloat32);
+  auto ws = torch::empty({2L * sampled_softmax_nsplit(B, S) * B}, f32);
+  auto loss = torch::empty({B}, f32), lse = torch::empty({B}, f32);
+  launch_sampled_softmax_fwd(h.data_ptr(), w_true.data_ptr(),
+                             w_samp.data_ptr(), ssm_f32(op, true_adj, B),
+                             ssm_f32(op, samp_adj, S), lp, sp,
+                             ws.data_ptr<float>(), lse.data_ptr<float>(),
+                             loss.data_ptr<float>(), (int)B, (int)S, (int)D,
+                             cur_stream());
+  return {loss, lse};
+}
+
+// g = dloss fp32 [B] -> (dh, dw_true, dw_samp bf16; dtrue_adj, dsamp_adj fp32)
+std::vector<torch::Tensor> sampled_softmax_bwd(
+    torch::Tensor h, torch::Tensor w_true, torch::Tensor w_samp,
+    OptTensor samp_adj, OptTensor labels, OptTensor sampled,
+    torch::Tensor lse, torch::Tensor loss, torch::Tensor g) {
+  const char* op = "sampled_softmax_bwd";
+  ssm_check_rows(op, h, w_true, w_samp);
+  const long B = h.size(0), S = w_samp.size(0), D = h.size(1);
+  const long *lp, *sp;
+  ssm_ids(op, labels, sampled, B, S, &lp, &sp);
+  auto f32 = h.options().dtype(torch::kFloat32);
+  auto dh = torch::empty_like(h), dw_true = torch::empty_like(w_true);
+  auto dw_samp = torch::empty_like(w_samp);
+  auto dtrue_adj = torch::empty({B}, f32), dsamp_adj = torch::empty({S}, f32);
+  launch_sampled_softmax_bwd(
+      h.data_ptr(), w_true.data_ptr(), w_samp.data_ptr(),
+      ssm_f32(op, samp_adj, S), lp, sp, ssm_f32(op, lse, B),
+      ssm_f32(op, loss, B), ssm_f32(op, g, B), dh.data_ptr(),
+      dw_true.data_ptr(), dw_samp.data_ptr(), dtrue_adj.data_ptr<float>(),
+      dsamp_adj.data_ptr<float>(), (int)B, (int)S, (int)D, cur_stream());
+  return {dh, dw_true, dw_samp, dtrue_adj, dsamp_adj};
+}
+
 torch::Tensor colsum(torch::Tensor x, torch::Tensor out) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
               x.is_contiguous() && x.dim() == 2, "colsum: bf16 [M,N]");
@@ -1563,4 +1652,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("diag"), py::arg("keep"), py::arg("out_f32"));
   m.def("dot_interaction_bwd", &dot_interaction_bwd, py::arg("x"),
         py::arg("dout"), py::arg("diag"), py::arg("keep"));
+  m.def("sampled_softmax_fwd", &sampled_softmax_fwd, py::arg("h"),
+        py::arg("w_true"), py::arg("w_samp"), py::arg("true_adj"),
+        py::arg("samp_adj"), py::arg("labels"), py::arg("sampled"));
+  m.def("sampled_softmax_bwd", &sampled_softmax_bwd, py::arg("h"),
+        py::arg("w_true"), py::arg("w_samp"), py::arg("samp_adj"),
+        py::arg("labels"), py::arg("sampled"), py::arg("lse"),
+        py::arg("loss"), py::arg("g"));
+  m.def("sampled_softmax_nsplit", &sampled_softmax_nsplit, py::arg("B"),
+        py::arg("S"));
 }
