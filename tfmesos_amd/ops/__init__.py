@@ -30,7 +30,9 @@ What a CTR model does with the pooled rows next: dot_interaction, the fused
 pairwise feature interaction (DLRM's dot interaction / an FM's Gram matrix),
 forward and backward. What a model with a large output vocabulary trains
 against: sampled_softmax_loss, the fused candidate-sampling loss (TF's
-sampled_softmax_loss; in-batch negatives), forward and backward.
+sampled_softmax_loss; in-batch negatives), forward and backward. A bag read
+as a sequence: bag_attention, fused softmax attention inside each CSR bag
+(target attention, self-attention, causal), forward and backward.
 """
 
 import collections
@@ -724,6 +726,153 @@ def sampled_softmax_loss(h, w_true, w_samp, true_adj=None, samp_adj=None,
     return _SampledSoftmaxFn.apply(h.contiguous(), w_true.contiguous(),
                                    w_samp.contiguous(), c(true_adj),
                                    c(samp_adj), c(labels), c(sampled))
+
+
+# ------------------------------------------------- attention over CSR bags
+
+BAG_ATTENTION_MAX_D = 128       # csrc/bag_attention.h: kBagAttnMaxD
+
+
+def _csr_check_cpu(offsets, n, what):
+    lens = offsets[1:] - offsets[:-1]
+    if int(offsets[0]) != 0 or int(offsets[-1]) != n or bool((lens < 0).any()):
+        raise ValueError("bag_attention: %s must be nondecreasing with "
+                         "%s[0] == 0 and %s[-1] == %d" % (what, what, what, n))
+
+
+def _bag_attention_cpu(q, k, v, offsets, kv_offsets, causal, scale):
+    """The reference: fp32 [n, H, D] from fp32 rows, one bag at a time
+    (differentiable by autograd). The offsets are valid CPU tensors."""
+    out = torch.zeros(q.shape)
+    qo, ko = offsets.tolist(), kv_offsets.tolist()
+    for b in range(len(qo) - 1):
+        i, j = slice(qo[b], qo[b + 1]), slice(ko[b], ko[b + 1])
+        if i.start == i.stop or j.start == j.stop:
+            continue                    # no keys: the rows stay zero
+        s = scale * torch.einsum("ihd,jhd->hij", q[i], k[j])
+        if causal:
+            above = torch.ones(s.shape[1:], dtype=torch.bool).triu(1)
+            s = s.masked_fill(above, float("-inf"))
+        out[i] = torch.einsum("hij,jhd->ihd", torch.softmax(s, -1), v[j])
+    return out
+
+
+class _BagAttentionFn(torch.autograd.Function):
+    """Differentiable bag_attention. GPU: csrc/bag_attention.hip, one MFMA
+    kernel forward, delta + one MFMA kernel backward (and the tile-prefix
+    kernel each way). CPU: the same op in plain fp32 torch, per bag; on a
+    device it is never reached — n == 0 or m == 0 there is all zeros."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, offsets, kv_offsets, causal, scale):
+        ctx.flags = (causal, scale)
+        ctx.launch = q.is_cuda and q.shape[0] > 0 and k.shape[0] > 0
+        lse = None
+        if ctx.launch:
+            out, lse = _ext().bag_attention_fwd(q, k, v, offsets, kv_offsets,
+                                                causal, scale)
+        elif q.is_cuda:
+            out = torch.zeros_like(q)
+        else:
+            out = _bag_attention_cpu(q.float(), k.float(), v.float(), offsets,
+                                     kv_offsets, causal, scale).to(q.dtype)
+        ctx.save_for_backward(q, k, v, offsets, kv_offsets, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, offsets, kv_offsets, out, lse = ctx.saved_tensors
+        causal, scale = ctx.flags
+        if ctx.launch:
+            dq, dk, dv = _ext().bag_attention_bwd(
+                q, k, v, out, lse, dout.contiguous(), offsets, kv_offsets,
+                causal, scale)
+        elif q.is_cuda:
+            dq, dk, dv = (torch.zeros_like(t) for t in (q, k, v))
+        else:
+            with torch.enable_grad():
+                x = [t.detach().float().requires_grad_(True)
+                     for t in (q, k, v)]
+                ref = _bag_attention_cpu(*x, offsets, kv_offsets, causal,
+                                         scale)
+                g = torch.autograd.grad(ref, x, dout.float(),
+                                        allow_unused=True)
+            dq, dk, dv = (torch.zeros_like(t) if d is None else d.to(t.dtype)
+                          for t, d in zip((q, k, v), g))
+        return dq, dk, dv, None, None, None, None
+
+
+def bag_attention(q, k, v, offsets, kv_offsets=None, causal=False,
+                  scale=None):
+    """Softmax attention inside each bag of a CSR-shaped request: a bag
+    treated as a sequence (DIN-style target attention / attention pooling;
+    self-attention over a history as in SASRec, BST).
+
+    q is bf16 [n, H, D], k and v are bf16 [m, H, D] (H heads of width D).
+    offsets is int64 [B+1] over the n query rows and kv_offsets int64 [B+1]
+    over the m key rows, both under the CSR contract of the pooled lookup
+    (validated on the CPU; the GPU path does not sync and clamps what it
+    derives from them). ``kv_offsets=None`` means ``offsets`` and m == n:
+    self-attention over each bag. For bag b, head h, query i and key j of
+    that bag
+
+        s = scale * q[i,h].k[j,h]          (scale defaults to D ** -0.5)
+        p = softmax over the kept j of s   (causal keeps j <= i, positions
+                                            inside the bag; self form only)
+        out[i,h] = sum_j p * v[j,h]
+
+    Returns out, bf16 [n, H, D]; scores, exp and sums are fp32,
+    max-subtracted, rounded once. A query whose bag has no keys gets a zero
+    row and contributes zero to every gradient. Differentiable in q, k, v
+    (bf16 gradients, accumulated in fp32 and rounded once; on the GPU p and
+    dS are rounded to bf16 on their way into the MFMA operand). ``k is v``
+    (one pulled row tensor for both) works: autograd adds the two gradients.
+
+    Target attention is q = one row per bag with ``offsets = arange(B+1)``
+    and the pulled rows of the bags' ids as k and v. The row gradient of
+    k / v is one row per position and feeds ``push(ids, grad)`` unchanged:
+    the sparse applies sum duplicates.
+
+    1 <= D <= 128 (BAG_ATTENTION_MAX_D), any H, n, m, B and base alignment.
+    GPU: csrc/bag_attention.hip — no padded [B, H, Lmax, Lmax] scores in
+    memory, no atomics, bit-reproducible, no host sync.
+    """
+    name = "bag_attention"
+    for t in (q, k, v):
+        if t.dim() != 3 or t.dtype != torch.bfloat16:
+            raise ValueError("%s: q, k, v must be bf16 [rows, H, D], got %s %s"
+                             % (name, t.dtype, tuple(t.shape)))
+    n, H, D = q.shape
+    m = k.shape[0]
+    if k.shape[1:] != (H, D) or v.shape != k.shape:
+        raise ValueError("%s: need q [n, H, D] and k, v [m, H, D], got %s %s %s"
+                         % (name, tuple(q.shape), tuple(k.shape),
+                            tuple(v.shape)))
+    if H < 1 or not 1 <= D <= BAG_ATTENTION_MAX_D:
+        raise ValueError("%s: H = %d, D = %d, need H >= 1 and 1 <= D <= %d"
+                         % (name, H, D, BAG_ATTENTION_MAX_D))
+    if causal and kv_offsets is not None:
+        raise ValueError("%s: causal needs self-attention (kv_offsets=None)"
+                         % name)
+    if kv_offsets is None:
+        if m != n:
+            raise ValueError("%s: kv_offsets=None needs m == n, got %d, %d"
+                             % (name, m, n))
+        kv_offsets = offsets
+    for t in (offsets, kv_offsets):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.numel() < 1:
+            raise ValueError("%s: offsets must be int64 [B+1]" % name)
+    if offsets.numel() != kv_offsets.numel():
+        raise ValueError("%s: offsets and kv_offsets differ in length" % name)
+    if not q.is_cuda:
+        _csr_check_cpu(offsets, n, "offsets")
+        _csr_check_cpu(kv_offsets, m, "kv_offsets")
+    offsets = offsets.contiguous()
+    kv_offsets = offsets if kv_offsets is offsets else kv_offsets.contiguous()
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    return _BagAttentionFn.apply(q.contiguous(), k.contiguous(),
+                                 v.contiguous(), offsets, kv_offsets,
+                                 bool(causal), scale)
 
 
 # ----------------------------------------------- row-sharded table routing

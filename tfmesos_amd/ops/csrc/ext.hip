@@ -14,6 +14,7 @@
 #include "interaction.h"
 #include "pool.h"
 #include "sampled_softmax.h"
+#include "bag_attention.h"
 #include "softmax_xent.h"
 
 namespace {
@@ -920,6 +921,106 @@ std::vector<torch::Tensor> sampled_softmax_bwd(
   return {dh, dw_true, dw_samp, dtrue_adj, dsamp_adj};
 }
 
+// Attention over CSR bags (bag_attention.hip): q [n,H,D], k, v [m,H,D] bf16,
+// offsets, kv_offsets int64 [B+1] (one tensor passed twice for
+// self-attention). The tile prefixes are computed on the device by each
+// call; nothing is read back.
+struct BagAttnDims { long n, m, B, H, D; };
+
+static BagAttnDims bag_attn_check(const char* op, const torch::Tensor& q,
+                                  const torch::Tensor& k,
+                                  const torch::Tensor& v,
+                                  const torch::Tensor& offsets,
+                                  const torch::Tensor& kv_offsets,
+                                  bool causal) {
+  for (const torch::Tensor* t : {&q, &k, &v})
+    TORCH_CHECK(t->is_cuda() && t->dim() == 3 && t->is_contiguous() &&
+                t->scalar_type() == torch::kBFloat16,
+                op, ": q, k, v must be contiguous bf16 [rows,H,D] on GPU");
+  const BagAttnDims d = {q.size(0), k.size(0), offsets.numel() - 1, q.size(1),
+                         q.size(2)};
+  TORCH_CHECK(d.n >= 1 && d.m >= 1 && d.H >= 1 && d.H <= 65535 && d.D >= 1 &&
+              d.D <= kBagAttnMaxD && k.size(1) == d.H && k.size(2) == d.D &&
+              v.sizes() == k.sizes(),
+              op, ": need q [n,H,D], k, v [m,H,D] with n, m >= 1, "
+              "1 <= H <= 65535 and 1 <= D <= ", kBagAttnMaxD);
+  TORCH_CHECK(i64_vec(offsets) && i64_vec(kv_offsets) && d.B >= 1 &&
+              kv_offsets.numel() == d.B + 1,
+              op, ": offsets and kv_offsets must be int64 [B+1] on GPU, "
+              "B >= 1");
+  TORCH_CHECK(bag_attention_max_tiles(d.n, d.B) +
+                      bag_attention_max_tiles(d.m, d.B) <= INT_MAX &&
+                  q.numel() <= INT_MAX && k.numel() <= INT_MAX,
+              op, ": the request is too large for one launch");
+  TORCH_CHECK(!causal || (d.m == d.n &&
+                          kv_offsets.data_ptr() == offsets.data_ptr()),
+              op, ": causal needs self-attention (kv_offsets is offsets)");
+  return d;
+}
+
+// -> int32 [2][B+1]: the tile prefixes of the query and of the key bags
+static torch::Tensor bag_attn_tiles(const BagAttnDims& d,
+                                    const torch::Tensor& offsets,
+                                    const torch::Tensor& kv_offsets) {
+  auto pre = torch::empty({2, d.B + 1}, offsets.options().dtype(torch::kInt32));
+  launch_bag_attention_tiles((const long*)offsets.data_ptr<int64_t>(),
+                             (const long*)kv_offsets.data_ptr<int64_t>(),
+                             pre.data_ptr<int>(), pre.data_ptr<int>() + d.B + 1,
+                             (int)d.n, (int)d.m, (int)d.B, cur_stream());
+  return pre;
+}
+
+// -> (out [n,H,D] bf16, lse [H,n] fp32)
+std::tuple<torch::Tensor, torch::Tensor> bag_attention_fwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor offsets,
+    torch::Tensor kv_offsets, bool causal, double scale) {
+  const BagAttnDims d =
+      bag_attn_check("bag_attention_fwd", q, k, v, offsets, kv_offsets, causal);
+  auto pre = bag_attn_tiles(d, offsets, kv_offsets);
+  auto out = torch::empty_like(q);
+  auto lse = torch::empty({d.H, d.n}, q.options().dtype(torch::kFloat32));
+  launch_bag_attention_fwd(
+      q.data_ptr(), k.data_ptr(), v.data_ptr(),
+      (const long*)offsets.data_ptr<int64_t>(),
+      (const long*)kv_offsets.data_ptr<int64_t>(), pre.data_ptr<int>(),
+      pre.data_ptr<int>() + d.B + 1, out.data_ptr(), lse.data_ptr<float>(),
+      (int)d.n, (int)d.m, (int)d.B, (int)d.H, (int)d.D, (float)scale, causal,
+      cur_stream());
+  return {out, lse};
+}
+
+// out, lse: the forward's; dout [n,H,D] bf16 -> (dq, dk, dv) bf16
+std::vector<torch::Tensor> bag_attention_bwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor out,
+    torch::Tensor lse, torch::Tensor dout, torch::Tensor offsets,
+    torch::Tensor kv_offsets, bool causal, double scale) {
+  const char* op = "bag_attention_bwd";
+  const BagAttnDims d =
+      bag_attn_check(op, q, k, v, offsets, kv_offsets, causal);
+  for (const torch::Tensor* t : {&out, &dout})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->scalar_type() == torch::kBFloat16 &&
+                t->sizes() == q.sizes(),
+                op, ": out and dout must be contiguous bf16 like q");
+  TORCH_CHECK(lse.is_cuda() && lse.is_contiguous() &&
+              lse.scalar_type() == torch::kFloat32 && lse.dim() == 2 &&
+              lse.size(0) == d.H && lse.size(1) == d.n,
+              op, ": lse must be fp32 [H,n]");
+  auto pre = bag_attn_tiles(d, offsets, kv_offsets);
+  auto delta = torch::empty_like(lse);
+  auto dq = torch::empty_like(q), dk = torch::empty_like(k);
+  auto dv = torch::empty_like(v);
+  launch_bag_attention_bwd(
+      q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+      dout.data_ptr(), (const long*)offsets.data_ptr<int64_t>(),
+      (const long*)kv_offsets.data_ptr<int64_t>(), pre.data_ptr<int>(),
+      pre.data_ptr<int>() + d.B + 1, lse.data_ptr<float>(),
+      delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+      (int)d.n, (int)d.m, (int)d.B, (int)d.H, (int)d.D, (float)scale, causal,
+      cur_stream());
+  return {dq, dk, dv};
+}
+
 torch::Tensor colsum(torch::Tensor x, torch::Tensor out) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
               x.is_contiguous() && x.dim() == 2, "colsum: bf16 [M,N]");
@@ -1661,4 +1762,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("loss"), py::arg("g"));
   m.def("sampled_softmax_nsplit", &sampled_softmax_nsplit, py::arg("B"),
         py::arg("S"));
+  m.def("bag_attention_fwd", &bag_attention_fwd, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("offsets"), py::arg("kv_offsets"),
+        py::arg("causal"), py::arg("scale"));
+  m.def("bag_attention_bwd", &bag_attention_bwd, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("dout"),
+        py::arg("offsets"), py::arg("kv_offsets"), py::arg("causal"),
+        py::arg("scale"));
 }

@@ -55,6 +55,8 @@
 
 namespace {
 
+#include "mfma_stream.h"
+
 constexpr int WAVES = 4;
 constexpr int OWN = WAVES * 16;   // owned rows per block
 constexpr int TILE = 64;          // streamed rows per tile
@@ -84,73 +86,11 @@ template <int DP> struct Smem {
   float mul[2][TILE];
 };
 
-// rows[row][k..k+8), zero outside [0,nrows) x [0,D)
-template <bool VEC>
-DEVINL bf16x8 ld_piece(const __bf16* __restrict__ rows, int row, int nrows,
-                       int k, int D) {
-  bf16x8 z = {};
-  if (VEC) {     // D % 8 == 0: a piece that starts inside the row ends inside
-    const bool ok = row < nrows && k < D;
-    const bf16x8 g = *(const bf16x8*)(rows + (ok ? (long)row * D + k : 0));
-    return ok ? g : z;
-  }
-  if (row < nrows) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (k + e < D) z[e] = rows[(long)row * D + k + e];
-  }
-  return z;
-}
-
-template <bool VEC>
-DEVINL void st_piece(__bf16* __restrict__ rows, int row, int k, int D,
-                     bf16x8 v) {
-  __bf16* dst = rows + (long)row * D + k;
-  if (VEC) {
-    *(bf16x8*)dst = v;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (k + e < D) dst[e] = v[e];
-  }
-}
-
-DEVINL bf16x4 tr_read(const __bf16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (__attribute__((address_space(3))) bf16x4*)p);
-}
-
-// MFMA B fragment out of a [row][d] image of stride XL: rows kfrag..kfrag+7
-// at column cb + (lane & 15), two transpose-reads of four image rows each
-// (lane mapping: gemm.hip, interaction.hip)
-template <int XL>
-DEVINL bf16x8 tr_frag(const __bf16* X, int kfrag, int cb, int lane) {
-  const int a = (kfrag + ((lane & 15) >> 2)) * XL + cb + 4 * (lane & 3);
-  const bf16x4 f0 = tr_read(&X[a]);
-  const bf16x4 f1 = tr_read(&X[a + 4 * XL]);
-  return __builtin_shufflevector(f0, f1, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// orders a wave's own LDS writes before its own LDS reads of other lanes'
-// data (the P image, the epilogue's parked tile)
-DEVINL void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // (m, s) <- merge of (m, s) and (m2, s2): s exp(m) + s2 exp(m2), max-factored
 DEVINL void lse_merge(float& m, float& s, float m2, float s2) {
   const float M = fmaxf(m, m2);
   s = s * __expf(m - M) + s2 * __expf(m2 - M);
   m = M;
-}
-
-// sum over the 16 lanes that share an accumulator row, fixed order
-DEVINL float row_sum16(float v) {
-#pragma unroll
-  for (int x = 1; x < 16; x <<= 1) v += __shfl_xor(v, x);
-  return v;
 }
 
 // One block's pass: owned tile `own_tile`, streamed tiles [t_begin, t_end).
@@ -181,7 +121,7 @@ DEVINL void pair_loop(const Args& a, Smem<DP>& sm, int own_tile, int t_begin,
   bf16x8 af[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
-    af[ks] = ld_piece<VEC>(own, arow, n_own, ks * 32 + kq, D);
+    af[ks] = ld_piece<VEC>(own, arow, n_own, ks * 32 + kq, D, D);
 
   // side values of this lane's 4 accumulator rows
   float o_add[4], o_mul[4];
@@ -211,7 +151,7 @@ DEVINL void pair_loop(const Args& a, Smem<DP>& sm, int own_tile, int t_begin,
 #pragma unroll
     for (int i = 0; i < PIECES; ++i) {
       const int q = tid + WAVES * WAVE * i;
-      pre[i] = ld_piece<VEC>(str, c0 + q / PPR, n_str, (q % PPR) * 8, D);
+      pre[i] = ld_piece<VEC>(str, c0 + q / PPR, n_str, (q % PPR) * 8, D, D);
     }
     if (tid < TILE) {
       const int row = c0 + tid;
@@ -369,7 +309,8 @@ DEVINL void pair_loop(const Args& a, Smem<DP>& sm, int own_tile, int t_begin,
     for (int i = 0; i < PIECES; ++i) {
       const int q = lane + WAVE * i;
       *(bf16x8*)&R[(q / PPR) * XL + (q % PPR) * 8] =
-          ld_piece<VEC>(a.w_true, row0 + q / PPR, n_own, (q % PPR) * 8, D);
+          ld_piece<VEC>(a.w_true, row0 + q / PPR, n_own, (q % PPR) * 8, D,
+                        D);
     }
     wave_lds_sync();
   }
@@ -392,7 +333,7 @@ DEVINL void pair_loop(const Args& a, Smem<DP>& sm, int own_tile, int t_begin,
     const int q = lane + WAVE * i;
     const int row = row0 + q / PPR, c = (q % PPR) * 8;
     if (row < n_own && c < D)
-      st_piece<VEC>(out, row, c, D,
+      st_piece<VEC>(out, row, c, D, D,
                     *(const bf16x8*)&R[(q / PPR) * XL + c]);
   }
 
@@ -407,7 +348,7 @@ DEVINL void pair_loop(const Args& a, Smem<DP>& sm, int own_tile, int t_begin,
           bf16x8 o;
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = (__bf16)(q * (float)af[ks][e]);
-          st_piece<VEC>(a.dw_true, arow, k, D, o);
+          st_piece<VEC>(a.dw_true, arow, k, D, D, o);
         }
       }
       if (lane < 16) a.dtrue_adj[arow] = q;
