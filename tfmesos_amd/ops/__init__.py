@@ -32,7 +32,9 @@ forward and backward. What a model with a large output vocabulary trains
 against: sampled_softmax_loss, the fused candidate-sampling loss (TF's
 sampled_softmax_loss; in-batch negatives), forward and backward. A bag read
 as a sequence: bag_attention, fused softmax attention inside each CSR bag
-(target attention, self-attention, causal), forward and backward.
+(target attention, self-attention, causal), forward and backward. Evaluating
+and serving over the whole vocabulary: dot_topk and dot_rank (TF's top_k /
+in_top_k over q @ w.T + bias), fused scoring and selection.
 """
 
 import collections
@@ -728,9 +730,131 @@ def sampled_softmax_loss(h, w_true, w_samp, true_adj=None, samp_adj=None,
                                    c(samp_adj), c(labels), c(sampled))
 
 
+# ------------------------------------- scoring over a whole vocabulary
+
+DOT_TOPK_MAX_D = 256            # csrc/retrieval.h: kDotTopkMaxD
+DOT_TOPK_MAX_K = 64             # csrc/retrieval.h: kDotTopkMaxK
+
+
+def dot_topk_nsplit(B, V):
+    """The number of vocabulary splits the GPU launcher chooses for B
+    queries against V items: a function of (B, V) only."""
+    return _ext().dot_topk_nsplit(int(B), int(V))
+
+
+def _retrieval_args(name, q, w, bias, splits):
+    """Checked (q, w, bias, splits-for-the-binding), detached."""
+    for t in (q, w):
+        if t.dim() != 2 or t.dtype != torch.bfloat16:
+            raise ValueError("%s: q, w must be bf16 matrices, got %s %s"
+                             % (name, t.dtype, tuple(t.shape)))
+    D, V = q.shape[1], w.shape[0]
+    if w.shape[1] != D:
+        raise ValueError("%s: need q [B, D] and w [V, D], got %s %s"
+                         % (name, tuple(q.shape), tuple(w.shape)))
+    if not 1 <= D <= DOT_TOPK_MAX_D:
+        raise ValueError("%s: D = %d, need 1 <= D <= %d"
+                         % (name, D, DOT_TOPK_MAX_D))
+    if not 1 <= V < 2 ** 31:
+        raise ValueError("%s: V = %d, need 1 <= V < 2**31" % (name, V))
+    if bias is not None and (bias.dtype != torch.float32
+                             or bias.shape != (V,)):
+        raise ValueError("%s: bias [V] must be fp32" % name)
+    if splits is not None and (int(splits) != splits or splits < 1):
+        raise ValueError("%s: splits = %r, need None or an integer >= 1"
+                         % (name, splits))
+    return (q.detach().contiguous(), w.detach().contiguous(),
+            None if bias is None else bias.detach().contiguous(),
+            0 if splits is None else int(splits))
+
+
+def _dot_scores(q, w, bias):
+    s = q.float() @ w.float().t()
+    return s if bias is None else s + bias
+
+
+def dot_topk(q, w, k, bias=None, splits=None):
+    """The k best items of a vocabulary for each query, without [B, V]
+    logits in memory (TF's ``top_k`` over ``q @ w.T + bias``; retrieval,
+    recall@k).
+
+    q is bf16 [B, D], w is bf16 [V, D], bias is fp32 [V] or None (0) and may
+    hold -inf to mask items out. The score is
+
+        s[b, j] = q[b].w[j] + bias[j]      (fp32 dot product, then the bias)
+
+    and one total order is used by this op and ``dot_rank``: item j BEATS
+    item i for a query iff s_j > s_i, or s_j == s_i and j < i.
+
+    Returns (values fp32 [B, k], indices int64 [B, k]): the k best items per
+    query, best first; a tie goes to the lowest index and -inf items come
+    last in index order. NaN scores are outside the contract. Not
+    differentiable: the inputs are taken detached.
+
+    1 <= D <= 256 (DOT_TOPK_MAX_D), 1 <= k <= 64 (DOT_TOPK_MAX_K),
+    k <= V < 2**31 (k > V raises, like ``torch.topk``), any B and base
+    alignment. ``splits=None`` lets the launcher split the vocabulary over
+    ``dot_topk_nsplit(B, V)`` blocks per 64 queries; an integer forces the
+    number, clamped to the number of 64-item tiles (the result does not
+    depend on it). GPU: csrc/retrieval.hip — MFMA scores and a per-row
+    running top-k in LDS, no atomics on floats, bit-reproducible, no host
+    sync. CPU: the [B, V] scores in fp32 and a stable descending sort.
+    """
+    name = "dot_topk"
+    q, w, bias, splits = _retrieval_args(name, q, w, bias, splits)
+    B, V = q.shape[0], w.shape[0]
+    if int(k) != k or not 1 <= k <= DOT_TOPK_MAX_K:
+        raise ValueError("%s: k = %r, need 1 <= k <= %d"
+                         % (name, k, DOT_TOPK_MAX_K))
+    if k > V:
+        raise ValueError("%s: k = %d exceeds V = %d" % (name, k, V))
+    k = int(k)
+    if B == 0:
+        return (torch.empty(0, k, device=q.device),
+                torch.empty(0, k, dtype=torch.int64, device=q.device))
+    if q.is_cuda:
+        return _ext().dot_topk(q, w, k, bias, splits)
+    values, indices = torch.sort(_dot_scores(q, w, bias), dim=1,
+                                 descending=True, stable=True)
+    return values[:, :k].contiguous(), indices[:, :k].contiguous()
+
+
+def dot_rank(q, w, labels, bias=None, splits=None):
+    """The rank of item labels[b] among all V items for query b (TF's
+    ``in_top_k`` for every k at once; HR@k, NDCG@k, MRR).
+
+    q, w, bias, the score and the order are those of ``dot_topk``; labels is
+    int64 [B] with values in [0, V) (validated on the CPU; the GPU path does
+    not sync, and a label outside the range gives a meaningless rank for its
+    query). Returns int64 [B]: the number of items that beat labels[b], so
+    ``rank[b] < k`` exactly when labels[b] is among ``dot_topk``'s indices —
+    on the GPU the label's score is computed by the same arithmetic as every
+    other item's, so a near-tie cannot count the item against itself. NaN
+    scores are outside the contract. Not differentiable.
+
+    Limits and ``splits`` as for ``dot_topk``. GPU: csrc/retrieval.hip.
+    """
+    name = "dot_rank"
+    q, w, bias, splits = _retrieval_args(name, q, w, bias, splits)
+    B, V = q.shape[0], w.shape[0]
+    if labels.dtype != torch.int64 or labels.shape != (B,):
+        raise ValueError("%s: labels [B] must be int64" % name)
+    labels = labels.contiguous()
+    if B == 0:
+        return torch.empty(0, dtype=torch.int64, device=q.device)
+    if q.is_cuda:
+        return _ext().dot_rank(q, w, labels, bias, splits)
+    if int(labels.min()) < 0 or int(labels.max()) >= V:
+        raise ValueError("%s: labels must lie in [0, %d)" % (name, V))
+    s = _dot_scores(q, w, bias)
+    t = s.gather(1, labels[:, None])
+    before = torch.arange(V)[None, :] < labels[:, None]
+    return ((s > t) | ((s == t) & before)).sum(1)
+
+
 # ------------------------------------------------- attention over CSR bags
 
-BAG_ATTENTION_MAX_D = 128       # csrc/bag_attention.h: kBagAttnMaxD
+BAG_ATTENTION_MAX_D = 128      # csrc/bag_attention.h: kBagAttnMaxD
 
 
 def _csr_check_cpu(offsets, n, what):

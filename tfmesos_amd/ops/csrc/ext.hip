@@ -14,6 +14,7 @@
 #include "interaction.h"
 #include "pool.h"
 #include "sampled_softmax.h"
+#include "retrieval.h"
 #include "bag_attention.h"
 #include "softmax_xent.h"
 
@@ -921,6 +922,65 @@ std::vector<torch::Tensor> sampled_softmax_bwd(
   return {dh, dw_true, dw_samp, dtrue_adj, dsamp_adj};
 }
 
+// Scoring over a whole vocabulary (retrieval.hip): q [B,D], w [V,D] bf16,
+// bias fp32 [V] or none. splits == 0 lets dot_topk_nsplit(B, V) choose.
+static void retrieval_check(const char* op, const torch::Tensor& q,
+                            const torch::Tensor& w, long splits) {
+  for (const torch::Tensor* t : {&q, &w})
+    TORCH_CHECK(t->is_cuda() && t->dim() == 2 && t->is_contiguous() &&
+                t->scalar_type() == torch::kBFloat16,
+                op, ": q, w must be contiguous bf16 matrices on GPU");
+  TORCH_CHECK(q.size(0) >= 1 && q.size(0) <= INT_MAX - 64 && w.size(0) >= 1 &&
+              w.size(0) <= INT_MAX && q.size(1) >= 1 &&
+              q.size(1) <= kDotTopkMaxD && w.size(1) == q.size(1) &&
+              splits >= 0,
+              op, ": need q [B,D], w [V,D] with B >= 1, 1 <= V < 2^31, "
+              "1 <= D <= ", kDotTopkMaxD, " and splits >= 0");
+}
+
+// -> (values fp32 [B,k], indices int64 [B,k])
+std::tuple<torch::Tensor, torch::Tensor> dot_topk(torch::Tensor q,
+                                                  torch::Tensor w, long k,
+                                                  OptTensor bias,
+                                                  long splits) {
+  const char* op = "dot_topk";
+  retrieval_check(op, q, w, splits);
+  const long B = q.size(0), V = w.size(0), D = q.size(1);
+  TORCH_CHECK(k >= 1 && k <= kDotTopkMaxK && k <= V,
+              op, ": need 1 <= k <= min(V, ", kDotTopkMaxK, ")");
+  const int nsplit = dot_topk_splits(B, V, splits);
+  auto i64 = q.options().dtype(torch::kInt64);
+  auto ws = torch::empty({nsplit, B, k}, i64);
+  auto values = torch::empty({B, k}, q.options().dtype(torch::kFloat32));
+  auto indices = torch::empty({B, k}, i64);
+  launch_dot_topk(q.data_ptr(), w.data_ptr(), ssm_f32(op, bias, V),
+                  (long*)ws.data_ptr<int64_t>(), values.data_ptr<float>(),
+                  (long*)indices.data_ptr<int64_t>(), (int)B, (int)V, (int)D,
+                  (int)k, nsplit, cur_stream());
+  return {values, indices};
+}
+
+// labels int64 [B] -> rank int64 [B]
+torch::Tensor dot_rank(torch::Tensor q, torch::Tensor w, torch::Tensor labels,
+                       OptTensor bias, long splits) {
+  const char* op = "dot_rank";
+  retrieval_check(op, q, w, splits);
+  const long B = q.size(0), V = w.size(0), D = q.size(1);
+  TORCH_CHECK(i64_vec(labels) && labels.size(0) == B,
+              op, ": labels [B] must be int64 on GPU");
+  const int nsplit = dot_topk_splits(B, V, splits);
+  auto i64 = q.options().dtype(torch::kInt64);
+  auto true_key = torch::empty({B}, i64), ws = torch::empty({nsplit, B}, i64);
+  auto rank = torch::empty({B}, i64);
+  launch_dot_rank(q.data_ptr(), w.data_ptr(), ssm_f32(op, bias, V),
+                  (const long*)labels.data_ptr<int64_t>(),
+                  (long*)true_key.data_ptr<int64_t>(),
+                  (long*)ws.data_ptr<int64_t>(),
+                  (long*)rank.data_ptr<int64_t>(), (int)B, (int)V, (int)D,
+                  nsplit, cur_stream());
+  return rank;
+}
+
 // Attention over CSR bags (bag_attention.hip): q [n,H,D], k, v [m,H,D] bf16,
 // offsets, kv_offsets int64 [B+1] (one tensor passed twice for
 // self-attention). The tile prefixes are computed on the device by each
@@ -1762,6 +1822,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("loss"), py::arg("g"));
   m.def("sampled_softmax_nsplit", &sampled_softmax_nsplit, py::arg("B"),
         py::arg("S"));
+  m.def("dot_topk", &dot_topk, py::arg("q"), py::arg("w"), py::arg("k"),
+        py::arg("bias"), py::arg("splits"));
+  m.def("dot_rank", &dot_rank, py::arg("q"), py::arg("w"), py::arg("labels"),
+        py::arg("bias"), py::arg("splits"));
+  m.def("dot_topk_nsplit", &dot_topk_nsplit, py::arg("B"), py::arg("V"));
   m.def("bag_attention_fwd", &bag_attention_fwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("offsets"), py::arg("kv_offsets"),
         py::arg("causal"), py::arg("scale"));

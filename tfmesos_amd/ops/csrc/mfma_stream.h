@@ -1,7 +1,8 @@
 // Device helpers shared by the kernels that own 64 rows as MFMA A fragments
 // and stream another row set through row-major LDS tiles
-// (sampled_softmax.hip, bag_attention.hip): guarded 16-byte row pieces with
-// a row stride, transpose reads of an LDS image, the wave-level LDS fence.
+// (sampled_softmax.hip, bag_attention.hip, retrieval.hip): guarded 16-byte
+// row pieces with a row stride, transpose reads of an LDS image, the
+// wave-level LDS fence.
 // Included after common.h, inside the including file's anonymous namespace
 // and its no-packed-fp32-ops attribute region, so that the helpers carry the
 // target features of the kernels they are inlined into.
