@@ -8,6 +8,14 @@ fused softmax-xent + fused relu-bwd on GPU) — no autograd in the hot
 path, so the step is a short fixed kernel sequence (2 kernels at the
 benchmark geometry: the one-launch split-K forward and the fused
 head+tail; GraphedStep can capture it and self-tunes graph-vs-eager).
+
+On the single-GPU fast path (``fwd_bwd_apply``) those two launches are
+bound once to the store's buffers (ops.mlp_sgd_step): nothing they
+check, look up or allocate changes from step to step but x and the
+labels, so a step is one call into native code that checks those two
+and launches. That keeps the host ahead of the ~11 us the GPU is busy
+per step, which is what lets eager launches compete with a hipGraph
+replay and its fixed cost per replay.
 """
 
 import math
@@ -20,6 +28,17 @@ from tfmesos_amd import ops
 # TFA_MLP_HEADTAIL=0 selects the previous head kernel + tail kernel
 # sequence (one more launch) for A/B comparison
 _HEADTAIL = os.environ.get("TFA_MLP_HEADTAIL", "1") != "0"
+# TFA_MLP_STEP=0 keeps ops.mlp_fwd_snap + ops.mlp_head_tail_sgd called
+# every step in place of the bound step (same kernels), for A/B comparison
+_STEP = os.environ.get("TFA_MLP_STEP", "1") != "0"
+
+
+def _fwd_takes_snapshot(B, M, H):
+    """Whether the forward x[B,M] @ w1[M,H] runs on the one-launch kernel
+    whose launch snapshots the classifier: the one route
+    ops.mlp_sgd_step binds."""
+    return ops._ext().gemm_plan(B, H, M, False, False, 1, False, 0)[0] \
+        == "fwd1"
 
 
 class MnistMLP(object):
@@ -30,6 +49,8 @@ class MnistMLP(object):
         self.inputs = image_pixels
         self.classes = classes
         self.seed = seed
+        self._step = None       # see _bound_step
+        self._step_key = None
 
     def param_specs(self):
         return [
@@ -137,6 +158,25 @@ class MnistMLP(object):
                 and x.shape[0] <= 128 and self.hidden <= 128
                 and self.classes <= 16)
 
+    def _bound_step(self, st, x, lr):
+        """The ops.mlp_sgd_step bound to store ``st``'s buffers, x's
+        shape and lr — rebuilt when any of those differ from the last
+        call's — or None where the forward takes no snapshot (the two
+        ops then run as before)."""
+        key = (st.flat.data_ptr(), st.flat_bf16.data_ptr(), tuple(x.shape),
+               float(lr))
+        if key != self._step_key:
+            B, M = x.shape
+            self._step = None
+            if _fwd_takes_snapshot(B, M, self.hidden):
+                s = lambda n: st.view(n, bf16=True)
+                self._step = ops.mlp_sgd_step(
+                    st.view("hid_w"), st.view("hid_b"), st.view("sm_w"),
+                    st.view("sm_b"), s("hid_w"), s("hid_b"), s("sm_w"),
+                    s("sm_b"), lr, B, M, self.hidden, self.classes)
+            self._step_key = key
+        return self._step
+
     def fwd_bwd_apply(self, trainer, x, y, lr):
         """One fused replica step (world==1 fast path): fwd GEMM
         (one launch, which also snapshots the 2 KB classifier
@@ -147,12 +187,20 @@ class MnistMLP(object):
         sequence (ops.mlp_head_fused -> ops.mlp_tail_sgd), which
         TFA_MLP_HEADTAIL=0 or a shape outside the fused kernel's
         limits selects (plain SGD, grad mean over the single worker
-        = 1).
+        = 1). On GPU the two launches come from the bound step
+        (_bound_step), whose loss tensor is its own: it holds this
+        step's loss until the next step.
         """
         st = trainer.store
         p = lambda n: st.view(n, bf16=True)
         g = trainer.grad_view
         if self._headtail_ok(x):
+            step = self._bound_step(st, x, lr) if _STEP and x.is_cuda \
+                else None
+            if step is not None:
+                loss = step.run(x, y)
+                st.global_step += 1
+                return loss
             # the fwd GEMM's launch snapshots W2/b2 on its way, so
             # the fused kernel can apply them without a ticket
             h, snap = ops.mlp_fwd_snap(x, p("hid_w"), p("hid_b"),

@@ -2535,6 +2535,25 @@ def mlp_head_tail_sgd(x, h, w2_s, b2_s, y, w1_m, b1_m, w2_m, b2_m,
     return loss
 
 
+def mlp_sgd_step(w1_m, b1_m, w2_m, b2_m, w1_s, b1_s, w2_s, b2_s, lr,
+                 B, M, H, C):
+    """mlp_fwd_snap + mlp_head_tail_sgd(snap=...) bound once to a
+    trainer's fp32 masters *_m and bf16 shadows *_s, a learning rate and
+    the geometry x [B,M] -> hidden H -> C classes (GPU only). Every check,
+    buffer and launch argument that stays the same from step to step is
+    settled here; ``step.run(x, y)`` checks x and the labels and launches
+    the same two kernels with the same arguments on the current stream,
+    so masters, shadows and loss are those of the two ops bit for bit,
+    eagerly or under graph capture. ``run`` returns the step's OWN 0-dim
+    loss tensor: it holds a step's loss until the next ``run`` (as the
+    loss of a replayed graph does) — copy it to keep it longer. The
+    buffers must stay where they are (PStore.load copies into them).
+    Raises where the forward of this geometry is not on the one-launch
+    kernel that takes the snapshot; the two ops serve every geometry."""
+    return _ext().MlpSgdStep(w1_m, b1_m, w2_m, b2_m, w1_s, b1_s, w2_s,
+                             b2_s, float(lr), B, M, H, C)
+
+
 def mlp_fwd_head_fused(x, w1, b1, w2, b2, labels, scale=None,
                        dw2=None, db2=None):
     """Whole MLP fwd + classifier head in TWO kernels (GPU): split-K

@@ -380,9 +380,9 @@ torch::Tensor gemm_bias_act_route(torch::Tensor a, torch::Tensor b,
 // of SnapArgs), or EMPTY when the GEMM took a kernel path that takes no
 // snapshot — the caller then uses the live shadow and the arrival
 // ticket.
-std::vector<torch::Tensor> mlp_fwd_snap(torch::Tensor x, torch::Tensor w1,
-                                        torch::Tensor b1, torch::Tensor w2s,
-                                        torch::Tensor b2s) {
+// The side job that snapshots the classifier shadow (w2s, b2s); the
+// caller points dst at its buffer of kSnapElems bf16.
+SnapArgs mlp_snap_args(const torch::Tensor& w2s, const torch::Tensor& b2s) {
   for (auto* t : {&w2s, &b2s})
     TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
                 t->scalar_type() == torch::kBFloat16,
@@ -390,14 +390,22 @@ std::vector<torch::Tensor> mlp_fwd_snap(torch::Tensor x, torch::Tensor w1,
   TORCH_CHECK(w2s.dim() == 2 && w2s.size(0) <= 128 && w2s.size(1) <= 16 &&
               w2s.size(1) >= 1 && b2s.numel() <= 16,
               "classifier too large for the snapshot buffer");
+  SnapArgs sa;
+  sa.s0 = w2s.data_ptr(); sa.s1 = b2s.data_ptr(); sa.dst = nullptr;
+  sa.n0 = (int)w2s.numel(); sa.n1 = (int)b2s.numel(); sa.off1 = kSnapB2Off;
+  sa.rows = (int)w2s.size(0); sa.cols = (int)w2s.size(1);
+  return sa;
+}
+
+std::vector<torch::Tensor> mlp_fwd_snap(torch::Tensor x, torch::Tensor w1,
+                                        torch::Tensor b1, torch::Tensor w2s,
+                                        torch::Tensor b2s) {
+  SnapArgs sa = mlp_snap_args(w2s, b2s);
   static std::unordered_map<int, torch::Tensor> smap;
   auto& sb = smap[x.device().index()];
   if (!sb.defined())
     sb = torch::zeros({kSnapElems}, w2s.options());
-  SnapArgs sa;
-  sa.s0 = w2s.data_ptr(); sa.s1 = b2s.data_ptr(); sa.dst = sb.data_ptr();
-  sa.n0 = (int)w2s.numel(); sa.n1 = (int)b2s.numel(); sa.off1 = kSnapB2Off;
-  sa.rows = (int)w2s.size(0); sa.cols = (int)w2s.size(1);
+  sa.dst = sb.data_ptr();
   bool taken = false;
   auto empty = torch::empty({0}, x.options());
   auto h = gemm_bias_act_impl(x, w1, b1, 1, false, false, empty, empty,
@@ -1593,36 +1601,51 @@ void mlp_tail_sgd(torch::Tensor x, torch::Tensor dh,
 // Shared argument checks of the fused head+tail ops: the limits of the
 // two kernels it replaces (head: B<=128, H<=128, H%4==0, C<=16; tail:
 // 2..512 32x32 tiles), returned as a filled HeadTailArgs.
-static HeadTailArgs head_tail_args(const torch::Tensor& x,
-                                   const torch::Tensor& h,
-                                   const torch::Tensor& w2,
-                                   const torch::Tensor& b2,
-                                   const torch::Tensor& y,
-                                   torch::Tensor& loss) {
+// In two halves, so that a bound step (MlpSgdStep) checks once what it
+// keeps and per run only what a call brings: x and the labels ...
+static void head_tail_check_xy(const torch::Tensor& x,
+                               const torch::Tensor& y) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
               x.scalar_type() == torch::kBFloat16, "x must be bf16 [B,M]");
+  TORCH_CHECK(y.is_cuda() && y.is_contiguous() &&
+              y.scalar_type() == torch::kInt64 && y.numel() == x.size(0),
+              "labels must be int64 [B]");
+  // rows of whole b128 chunks are loaded as such; ragged rows by element
+  TORCH_CHECK((x.size(1) & 7) != 0 || (uintptr_t)x.data_ptr() % 16 == 0,
+              "x must be 16-byte aligned where M % 8 == 0");
+}
+
+// ... and h, the classifier and the geometry [B,M] of x.
+static void head_tail_check_fixed(long B, long M, const torch::Tensor& h,
+                                  const torch::Tensor& w2,
+                                  const torch::Tensor& b2) {
   TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() &&
               h.scalar_type() == torch::kBFloat16 &&
-              h.size(0) == x.size(0), "h must be bf16 [B,H]");
+              h.size(0) == B, "h must be bf16 [B,H]");
   TORCH_CHECK(w2.is_cuda() && w2.dim() == 2 && w2.is_contiguous() &&
               w2.scalar_type() == torch::kBFloat16 &&
               w2.size(0) == h.size(1), "w2 must be bf16 [H,C]");
-  const long B = x.size(0), M = x.size(1), H = h.size(1), C = w2.size(1);
+  const long H = h.size(1), C = w2.size(1);
   TORCH_CHECK(b2.is_cuda() && b2.is_contiguous() &&
               b2.scalar_type() == torch::kBFloat16 && b2.numel() == C,
               "b2 must be bf16 [C]");
-  TORCH_CHECK(y.is_cuda() && y.is_contiguous() &&
-              y.scalar_type() == torch::kInt64 && y.numel() == B,
-              "labels must be int64 [B]");
   TORCH_CHECK(B >= 1 && B <= 128 && H <= 128 && (H & 3) == 0 && C >= 1 &&
               C <= 16, "mlp_head_tail limits: B<=128, H<=128, H%4==0, "
               "C<=16");
   const long stiles = ((M + 31) / 32) * ((H + 31) / 32);
   TORCH_CHECK(stiles >= 2 && stiles <= 512,
               "shape outside the small-GEMM regime");
-  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
-              (uintptr_t)h.data_ptr() % 8 == 0,
-              "x must be 16-byte and h 8-byte aligned");
+  TORCH_CHECK((uintptr_t)h.data_ptr() % 8 == 0, "h must be 8-byte aligned");
+}
+
+static HeadTailArgs head_tail_args(const torch::Tensor& x,
+                                   const torch::Tensor& h,
+                                   const torch::Tensor& w2,
+                                   const torch::Tensor& b2,
+                                   const torch::Tensor& y,
+                                   torch::Tensor& loss) {
+  head_tail_check_xy(x, y);
+  head_tail_check_fixed(x.size(0), x.size(1), h, w2, b2);
   loss = torch::empty({}, h.options().dtype(torch::kFloat32));
   HeadTailArgs a = {};
   a.h = h.data_ptr();
@@ -1630,9 +1653,56 @@ static HeadTailArgs head_tail_args(const torch::Tensor& x,
   a.b2 = b2.data_ptr();
   a.labels = y.data_ptr<long>();
   a.loss = loss.data_ptr<float>();
-  a.scale = 1.0f / (float)B;
-  a.C = (int)C;
+  a.scale = 1.0f / (float)x.size(0);
+  a.C = (int)w2.size(1);
   return a;
+}
+
+// The plain-SGD apply of the sgd-mode kernel: fp32 masters *m and bf16
+// shadows *s of W1 [M,H], b1 [H], W2 and b2, checked.
+static SmallSgdArgs head_tail_sgd_args(
+    int M, int H, const torch::Tensor& w1m, const torch::Tensor& b1m,
+    const torch::Tensor& w2m, const torch::Tensor& b2m,
+    const torch::Tensor& w1s, const torch::Tensor& b1s,
+    const torch::Tensor& w2s, const torch::Tensor& b2s, double lr) {
+  for (auto* t : {&w1m, &b1m, &w2m, &b2m})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->scalar_type() == torch::kFloat, "masters must be fp32");
+  for (auto* t : {&w1s, &b1s})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->scalar_type() == torch::kBFloat16,
+                "shadows must be bf16");
+  TORCH_CHECK(w1m.numel() == (long)M * H && b1m.numel() == H &&
+              w1s.numel() == w1m.numel() && b1s.numel() == H,
+              "W1/b1 shape mismatch");
+  TORCH_CHECK(w2m.numel() == w2s.numel() && b2m.numel() == b2s.numel(),
+              "W2/b2 master/shadow shape mismatch");
+  SmallSgdArgs sga = {};
+  sga.pmw = (float*)w1m.data_ptr();
+  sga.psw = w1s.data_ptr();
+  sga.pmb = (float*)b1m.data_ptr();
+  sga.psb = b1s.data_ptr();
+  sga.pm2w = (float*)w2m.data_ptr();
+  sga.ps2w = w2s.data_ptr();
+  sga.pm2b = (float*)b2m.data_ptr();
+  sga.ps2b = b2s.data_ptr();
+  sga.lr = (float)lr;
+  sga.n2w = (int)w2m.numel();
+  sga.n2b = (int)b2m.numel();
+  return sga;
+}
+
+// W2/b2 as the forward's launch copied them into snap (mlp_snap_args):
+// the kernel reads those, and no ticket is needed
+static void head_tail_read_snap(HeadTailArgs* hta, const torch::Tensor& snap) {
+  TORCH_CHECK(snap.is_cuda() && snap.is_contiguous() &&
+              snap.scalar_type() == torch::kBFloat16 &&
+              snap.numel() >= kSnapElems &&
+              (uintptr_t)snap.data_ptr() % 16 == 0,
+              "snap must be mlp_fwd_snap's buffer");
+  hta->w2 = snap.data_ptr();
+  hta->b2 = (const bf16_t*)snap.data_ptr() + kSnapB2Off;
+  hta->ticket = nullptr;
 }
 
 // arrival ticket of the sgd-mode kernel: one zeroed device word per
@@ -1662,47 +1732,102 @@ torch::Tensor mlp_head_tail_sgd(torch::Tensor x, torch::Tensor h,
   torch::Tensor loss;
   HeadTailArgs hta = head_tail_args(x, h, w2s, b2s, y, loss);
   const int B = (int)x.size(0), M = (int)x.size(1), H = (int)h.size(1);
-  for (auto* t : {&w1m, &b1m, &w2m, &b2m})
-    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
-                t->scalar_type() == torch::kFloat, "masters must be fp32");
-  for (auto* t : {&w1s, &b1s})
-    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
-                t->scalar_type() == torch::kBFloat16,
-                "shadows must be bf16");
-  TORCH_CHECK(w1m.numel() == (long)M * H && b1m.numel() == H &&
-              w1s.numel() == w1m.numel() && b1s.numel() == H,
-              "W1/b1 shape mismatch");
-  TORCH_CHECK(w2m.numel() == w2s.numel() && b2m.numel() == b2s.numel(),
-              "W2/b2 master/shadow shape mismatch");
-  if (snap.numel() > 0) {
-    // W2/b2 as mlp_fwd_snap's launch copied them: no ticket needed
-    TORCH_CHECK(snap.is_cuda() && snap.is_contiguous() &&
-                snap.scalar_type() == torch::kBFloat16 &&
-                snap.numel() >= kSnapElems &&
-                (uintptr_t)snap.data_ptr() % 16 == 0,
-                "snap must be mlp_fwd_snap's buffer");
-    hta.w2 = snap.data_ptr();
-    hta.b2 = (const bf16_t*)snap.data_ptr() + kSnapB2Off;
-    hta.ticket = nullptr;
-  } else {
+  const SmallSgdArgs sga = head_tail_sgd_args(M, H, w1m, b1m, w2m, b2m, w1s,
+                                              b1s, w2s, b2s, lr);
+  if (snap.numel() > 0)
+    head_tail_read_snap(&hta, snap);
+  else
     hta.ticket = head_tail_ticket(x.device());
-  }
-  SmallSgdArgs sga = {};
-  sga.pmw = (float*)w1m.data_ptr();
-  sga.psw = w1s.data_ptr();
-  sga.pmb = (float*)b1m.data_ptr();
-  sga.psb = b1s.data_ptr();
-  sga.pm2w = (float*)w2m.data_ptr();
-  sga.ps2w = w2s.data_ptr();
-  sga.pm2b = (float*)b2m.data_ptr();
-  sga.ps2b = b2s.data_ptr();
-  sga.lr = (float)lr;
-  sga.n2w = (int)w2m.numel();
-  sga.n2b = (int)b2m.numel();
   launch_mlp_head_tail((const bf16_t*)x.data_ptr(), &hta, nullptr, nullptr,
                        false, M, H, B, &sga, cur_stream());
   return loss;
 }
+
+// The single-GPU mnist step bound once to a trainer's buffers: the
+// forward on gemm_fwd1_kernel, whose launch snapshots the classifier
+// shadow, then mlp_head_tail_kernel in its snapshot mode — the launches
+// of mlp_fwd_snap + mlp_head_tail_sgd with the same arguments, so the
+// same bits. Everything those two ops check, look up or allocate that
+// stays the same from step to step is done here once; run() checks x and
+// the labels and launches.
+class MlpSgdStep {
+ public:
+  MlpSgdStep(torch::Tensor w1m, torch::Tensor b1m, torch::Tensor w2m,
+             torch::Tensor b2m, torch::Tensor w1s, torch::Tensor b1s,
+             torch::Tensor w2s, torch::Tensor b2s, double lr, long B, long M,
+             long H, long C)
+      : keep_{w1m, b1m, w2m, b2m, w1s, b1s, w2s, b2s},
+        dev_(w1s.device()), B_(B), M_(M), H_(H) {
+    for (auto& t : keep_)
+      TORCH_CHECK(t.is_cuda() && t.device() == dev_,
+                  "mlp_sgd_step: masters and shadows on one GPU");
+    // the forward's operands, as gemm_bias_act_impl asks of them
+    TORCH_CHECK(w1s.scalar_type() == torch::kBFloat16 &&
+                w1s.is_contiguous() && w1s.dim() == 2 && w1s.size(0) == M &&
+                w1s.size(1) == H, "mlp_sgd_step: w1s must be bf16 [M,H]");
+    TORCH_CHECK(b1s.scalar_type() == torch::kBFloat16 && b1s.numel() == H,
+                "mlp_sgd_step: b1s must be bf16 [H]");
+    TORCH_CHECK(B >= 1 && M >= 1 && H >= 1 && w2s.dim() == 2 &&
+                w2s.size(1) == C, "mlp_sgd_step: geometry mismatch");
+    const GemmPlan plan = gemm_plan_of((int)B, (int)H, (int)M, false, false,
+                                       1, false, 0);
+    TORCH_CHECK(plan.kernel == kGemmFwd1,
+                "mlp_sgd_step: the forward of [", B, ",", M, "] x [", M, ",",
+                H, "] is not on the one-launch kernel that takes the "
+                "snapshot; use mlp_fwd_snap + mlp_head_tail_sgd");
+    kc_ = plan.sk.kc;
+    nslice_ = plan.sk.nslice;
+    vecb_ = vec_level(w1s.data_ptr(), H);
+    h_ = torch::empty({B, H}, w1s.options());
+    snap_ = torch::zeros({kSnapElems}, w1s.options());
+    loss_ = torch::zeros({}, w1s.options().dtype(torch::kFloat32));
+    sa_ = mlp_snap_args(w2s, b2s);
+    sa_.dst = snap_.data_ptr();
+    head_tail_check_fixed(B, M, h_, w2s, b2s);
+    hta_ = {};
+    hta_.h = h_.data_ptr();
+    hta_.loss = loss_.data_ptr<float>();
+    hta_.scale = 1.0f / (float)B;
+    hta_.C = (int)C;
+    head_tail_read_snap(&hta_, snap_);
+    sga_ = head_tail_sgd_args((int)M, (int)H, w1m, b1m, w2m, b2m, w1s, b1s,
+                              w2s, b2s, lr);
+  }
+
+  torch::Tensor run(const torch::Tensor& x, const torch::Tensor& y) {
+    head_tail_check_xy(x, y);
+    TORCH_CHECK(x.size(0) == B_ && x.size(1) == M_,
+                "mlp_sgd_step: x must be the [", B_, ",", M_,
+                "] the step was built for");
+    TORCH_CHECK(x.device() == dev_ && y.device() == dev_ &&
+                at::cuda::current_device() == dev_.index(),
+                "mlp_sgd_step: x, y and the current device must be the "
+                "step's GPU");
+    const bf16_t* xp = (const bf16_t*)x.data_ptr();
+    const hipStream_t stream = cur_stream();
+    bool taken;
+    launch_gemm_fwd1(xp, (const bf16_t*)keep_[4].data_ptr(),
+                     keep_[5].data_ptr(), /*bias_bf16=*/true, h_.data_ptr(),
+                     /*out_f32=*/false, /*relu=*/1, kc_, nslice_, (int)B_,
+                     (int)H_, (int)M_, (int)M_, (int)H_, (int)H_,
+                     vec_level(xp, M_), vecb_, /*variant=*/-1, &sa_, &taken,
+                     stream);
+    hta_.labels = y.data_ptr<long>();
+    launch_mlp_head_tail(xp, &hta_, nullptr, nullptr, false, (int)M_,
+                         (int)H_, (int)B_, &sga_, stream);
+    return loss_;
+  }
+
+ private:
+  torch::Tensor keep_[8];      // the bound buffers stay alive, in place
+  torch::Tensor h_, snap_, loss_;
+  torch::Device dev_;
+  long B_, M_, H_;
+  int kc_, nslice_, vecb_;
+  SnapArgs sa_;
+  HeadTailArgs hta_;
+  SmallSgdArgs sga_;
+};
 
 // grads mode of the same kernel (the distributed worker path): dW1,
 // db1, dW2, db2 are stored in the flat grad buffer's dtype (fp32 or
@@ -1777,6 +1902,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlp_tail_sgd", &mlp_tail_sgd);
   m.def("mlp_head_tail_sgd", &mlp_head_tail_sgd);
   m.def("mlp_fwd_snap", &mlp_fwd_snap);
+  py::class_<MlpSgdStep>(m, "MlpSgdStep")
+      .def(py::init<torch::Tensor, torch::Tensor, torch::Tensor,
+                    torch::Tensor, torch::Tensor, torch::Tensor,
+                    torch::Tensor, torch::Tensor, double, long, long, long,
+                    long>(),
+           py::arg("w1_m"), py::arg("b1_m"), py::arg("w2_m"),
+           py::arg("b2_m"), py::arg("w1_s"), py::arg("b1_s"),
+           py::arg("w2_s"), py::arg("b2_s"), py::arg("lr"), py::arg("B"),
+           py::arg("M"), py::arg("H"), py::arg("C"))
+      .def("run", &MlpSgdStep::run, py::arg("x"), py::arg("y"),
+           "One step on the current stream; returns the step's own loss "
+           "tensor, valid until the next run.");
   m.def("mlp_head_tail_grads", &mlp_head_tail_grads);
   m.def("gemm_sgd_pair", &gemm_sgd_pair);
   // the kernel path, K slicing and staging level a GEMM call takes
