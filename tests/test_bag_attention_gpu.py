@@ -5,8 +5,8 @@ Query bags (0, 1, 63, 64, 65, 130): an empty bag, one row, the tile edges and
 three tiles with a tail (so the causal form skips tiles and masks diagonal
 ones). The cross form's key bags (5, 0, 64, 130, 1, 65) put keys against no
 query and a query against no keys. D = 7 takes the guarded path, 8 is under
-one K step, 64 is exactly DP, 72 has a K tail inside DP = 128, 128 is the
-limit.
+one K step, 64 is exactly DP, 65 the first width of DP = 128 (guarded), 72
+has a K tail inside DP = 128, 128 is the limit.
 """
 
 import pytest
@@ -26,7 +26,7 @@ def gpu(inp):
 
 @pytest.mark.parametrize("causal", [False, True])
 @pytest.mark.parametrize("H", [1, 3])
-@pytest.mark.parametrize("D", [7, 8, 64, 72, 128])
+@pytest.mark.parametrize("D", [7, 8, 64, 65, 72, 128])
 def test_self_within_bounds(D, H, causal):
     check(gpu(make(QL, None, H, D)), causal)
 

@@ -2,7 +2,9 @@
 fp64 oracle of test_dot_topk.py.
 
 Exact cases (torch.equal): D = 7 takes the guarded path, 8 is under one K
-step, 72 has steps and a tail, 256 is the widest tile. (B, V, k) = (5, 130,
+step, 72 has steps and a tail, 256 is the widest tile; 64 | 65 and 128 | 129
+(at (5, 130, 1) only) are the two sides of the register-tile dispatch.
+(B, V, k) = (5, 130,
 1 / 10): three splits of one tile, an item tail; (67, 65, 64): two owned
 tiles with a tail, a tile plus one item, k at its limit; (1, 64, 64): one
 full tile, k == V; (130, 5, 5): V below a tile, k == V, three owned tiles;
@@ -28,6 +30,8 @@ EXACT = [("pairs", B, V, D, k, splits, n)
                                     (67, 65, 64, None, 2), (1, 64, 64, None, 1),
                                     (130, 5, 5, None, 1),
                                     (3, 387, 64, 1, None))]
+EXACT += [("pairs", 5, 130, D, 1, None, 3)      # the register-tile dispatch
+          for D in (64, 65, 128, 129)]
 EXACT += [(kind, 3, 387, 8, k, 1, None)
           for kind in ("ascending", "descending") for k in (64, 1)]
 EXACT += [("masked", 1, 64, 8, 64, None, 1),

@@ -2,7 +2,8 @@
 fp64 oracle and the derived bounds of test_sampled_softmax.py.
 
 D = 7 takes the guarded path, 8 is under one K step, 72 has steps and a
-tail, 200 and 256 (the limit) use the widest register tile. (B, S) =
+tail, 200 and 256 (the limit) use the widest register tile; 64 | 65 and
+128 | 129 are the two sides of the register-tile dispatch. (B, S) =
 (5, 130): one owned tile, three forward splits, a candidate tail; (67, 65):
 an owned-tile tail in both roles, a tile plus one; (130, 5): fewer
 candidates than a tile, three example tiles for the candidate-owning role;
@@ -24,8 +25,14 @@ def gpu(inp):
     return {k: v.to(DEV) for k, v in inp.items()}
 
 
-@pytest.mark.parametrize("D", [7, 8, 72, 200, 256])
-@pytest.mark.parametrize("B,S", [(5, 130), (67, 65), (130, 5), (1, 64)])
+BOUNDARY_D = [64, 65, 128, 129]     # both sides of each DP boundary
+
+
+@pytest.mark.parametrize(
+    "B,S,D",
+    [(B, S, D) for D in [7, 8, 72, 200, 256]
+     for B, S in [(5, 130), (67, 65), (130, 5), (1, 64)]]
+    + [(67, 65, D) for D in BOUNDARY_D])
 def test_fwd_bwd_within_bounds(B, S, D):
     check(gpu(make(B, S, D)))
 

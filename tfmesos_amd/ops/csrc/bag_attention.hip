@@ -17,7 +17,8 @@
 // (bag, tile) by binary search in the prefix and leaves if it is past the
 // total. blockIdx.y is the head; row r of head h starts at (r H + h) D.
 //
-// One loop (attn_loop) serves the three roles. A block of 4 waves OWNS 64
+// One loop (attn_loop) serves the three roles, on the scheme of
+// mfma_stream.h. A block of 4 waves OWNS 64
 // rows of one bag and head — wave w the rows 16w..16w+15, as MFMA A
 // fragments in registers, one or two tensors — and STREAMS the bag's rows of
 // the other side, two tensors, through LDS in tiles of 64 rows, row-major
@@ -64,11 +65,6 @@ namespace {
 
 #include "mfma_stream.h"
 
-constexpr int WAVES = 4;
-constexpr int OWN = WAVES * 16;   // owned rows per block
-constexpr int TILE = 64;          // streamed rows per tile
-constexpr int PL = TILE + 8;      // P image row stride
-constexpr float NEG = -1e30f;     // "no kept score yet": finite
 enum { FWD = 0, ROLE_Q = 1, ROLE_K = 2 };
 
 struct Args {
@@ -119,12 +115,8 @@ DEVINL bool locate(const int* __restrict__ pre, int B, int bid, int& bag,
 
 template <int ROLE, int DP, bool VEC>
 DEVINL void attn_loop(const Args& a, Smem<DP>& sm, int bid, int head) {
-  constexpr int XL = DP + 8;
-  constexpr int KS = DP / 32;       // K steps of the scores
-  constexpr int NT = DP / 16;       // 16-column tiles of the output rows
-  constexpr int PIECES = TILE * (DP / 8) / (WAVES * WAVE);   // == KS
-  constexpr int PPR = DP / 8;       // 16-byte pieces per image row
-  constexpr int ST = TILE / 16;     // 16-column tiles of the scores
+  typedef Stream<DP> G;
+  constexpr int NT = G::NT;
   constexpr bool OWN_Q = ROLE != ROLE_K;   // the owned rows are queries
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
@@ -155,16 +147,10 @@ DEVINL void attn_loop(const Args& a, Smem<DP>& sm, int bid, int head) {
   const long side = (long)head * a.n;       // lse / delta are [H,n]
 
   const int row0 = own0 + wave * 16;
-  const int arow = row0 + (lane & 15);      // this lane's A-fragment row
-  const int kq = (lane >> 4) << 3;          // its K offset inside a step
 
-  bf16x8 af1[KS], af2[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    af1[ks] = ld_piece<VEC>(own1, arow, own_end, ks * 32 + kq, D, rs);
-    if (ROLE != FWD)
-      af2[ks] = ld_piece<VEC>(own2, arow, own_end, ks * 32 + kq, D, rs);
-  }
+  bf16x8 af1[G::KS], af2[G::KS];
+  load_owned<DP, VEC>(af1, own1, row0, own_end, D, rs, lane);
+  if (ROLE != FWD) load_owned<DP, VEC>(af2, own2, row0, own_end, D, rs, lane);
 
   // this lane's 4 accumulator rows: position inside the bag, side values
   int o_pos[4];
@@ -172,8 +158,8 @@ DEVINL void attn_loop(const Args& a, Smem<DP>& sm, int bid, int head) {
   float o_lse[4], o_del[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int row = row0 + (lane >> 4) * 4 + r;
-    o_pos[r] = tile * OWN + wave * 16 + (lane >> 4) * 4 + r;
+    const int row = row0 + acc_row(lane, r);
+    o_pos[r] = tile * OWN + wave * 16 + acc_row(lane, r);
     o_ok[r] = row < own_end;
     o_lse[r] = o_del[r] = 0.f;
     if (ROLE == ROLE_Q && o_ok[r]) {
@@ -183,18 +169,13 @@ DEVINL void attn_loop(const Args& a, Smem<DP>& sm, int bid, int head) {
   }
 
   // streamed tile t: global -> registers (fetch), registers -> LDS (stash)
-  bf16x8 pre1[PIECES], pre2[PIECES];
+  bf16x8 pre1[G::PIECES], pre2[G::PIECES];
   float pre_lse = 0.f, pre_del = 0.f;
   auto fetch = [&](int t) {
     const int c0 = str_lo + t * TILE;
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-      const int p = tid + WAVES * WAVE * i;
-      pre1[i] = ld_piece<VEC>(str1, c0 + p / PPR, str_end, (p % PPR) * 8, D,
-                              rs);
-      pre2[i] = ld_piece<VEC>(str2, c0 + p / PPR, str_end, (p % PPR) * 8, D,
-                              rs);
-    }
+    auto src = [&](int trow) { return c0 + trow < str_end ? c0 + trow : -1; };
+    tile_fetch<DP, VEC>(pre1, str1, D, rs, tid, src);
+    tile_fetch<DP, VEC>(pre2, str2, D, rs, tid, src);
     if (ROLE == ROLE_K && tid < TILE) {
       const int row = c0 + tid;
       const bool ok = row < str_end;
@@ -203,12 +184,8 @@ DEVINL void attn_loop(const Args& a, Smem<DP>& sm, int bid, int head) {
     }
   };
   auto stash = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-      const int p = tid + WAVES * WAVE * i;
-      *(bf16x8*)&sm.T1[buf][(p / PPR) * XL + (p % PPR) * 8] = pre1[i];
-      *(bf16x8*)&sm.T2[buf][(p / PPR) * XL + (p % PPR) * 8] = pre2[i];
-    }
+    tile_stash<DP>(sm.T1[buf], pre1, tid);
+    tile_stash<DP>(sm.T2[buf], pre2, tid);
     if (ROLE == ROLE_K && tid < TILE) {
       sm.lse[buf][tid] = pre_lse;
       sm.del[buf][tid] = pre_del;
@@ -222,59 +199,17 @@ DEVINL void attn_loop(const Args& a, Smem<DP>& sm, int bid, int head) {
   f32x4 accB[NT] = {};              // dK (ROLE_K only)
   __bf16* P = sm.P[wave];
 
-  // 16 x 64 scores of the owned fragments against a streamed tile
-  auto scores = [&](const bf16x8 (&af)[KS], const __bf16* T, f32x4 (&acc)[ST]) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      if (ks * 32 < D) {
-#pragma unroll
-        for (int nt = 0; nt < ST; ++nt) {
-          const bf16x8 b = *(const bf16x8*)&T[(nt * 16 + (lane & 15)) * XL +
-                                              ks * 32 + kq];
-          acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks], b, acc[nt],
-                                                            0, 0, 0);
-        }
-      }
-    }
-  };
-  // acc += image . T: the image is the A operand, the B fragments come back
-  // from the row-major tile through transpose reads
-  auto image_times = [&](const __bf16* T, f32x4 (&acc)[NT]) {
-    wave_lds_sync();
-#pragma unroll
-    for (int k2 = 0; k2 < TILE / 32; ++k2) {
-      const bf16x8 pa = *(const bf16x8*)&P[(lane & 15) * PL + k2 * 32 + kq];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        if (nt * 16 < D) {
-          const bf16x8 b = tr_frag<XL>(T, k2 * 32 + kq, nt * 16, lane);
-          acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, b, acc[nt], 0,
-                                                            0, 0);
-        }
-      }
-    }
-    wave_lds_sync();                // the image is rewritten next
-  };
-
-  if (t_begin < t_end) {
-    fetch(t_begin);
-    stash(0);
-  }
-  __syncthreads();
-  for (int t = t_begin; t < t_end; ++t) {
-    const int buf = (t - t_begin) & 1;
-    const bool more = t + 1 < t_end;    // block-uniform
-    if (more) fetch(t + 1);
+  stream_tiles(t_begin, t_end, fetch, stash, [&](int t, int buf) {
     const __bf16* T1 = sm.T1[buf];
     const __bf16* T2 = sm.T2[buf];
 
     f32x4 acc[ST] = {};
-    scores(af1, T1, acc);
+    score_tile<DP>(af1, T1, acc, D, lane);
 
     bool kept[4][ST];
 #pragma unroll
     for (int nt = 0; nt < ST; ++nt) {
-      const int s_pos = t * TILE + nt * 16 + (lane & 15);
+      const int s_pos = t * TILE + nt * 16 + frag_row(lane);
       const bool s_ok = s_pos < str_end - str_lo;
 #pragma unroll
       for (int r = 0; r < 4; ++r)
@@ -302,20 +237,20 @@ DEVINL void attn_loop(const Args& a, Smem<DP>& sm, int bid, int head) {
         for (int nt = 0; nt < ST; ++nt) {
           const float p = kept[r][nt] ? __expf(sc[nt] - mx) : 0.f;
           s += p;
-          P[((lane >> 4) * 4 + r) * PL + nt * 16 + (lane & 15)] = (__bf16)p;
+          P[acc_row(lane, r) * PL + nt * 16 + frag_row(lane)] = (__bf16)p;
         }
         run_l[r] = run_l[r] * alpha + s;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) accA[nt][r] *= alpha;
       }
-      image_times(T2, accA);
+      image_times_tile<DP>(P, T2, accA, D, lane);
     } else {
       f32x4 accp[ST] = {};
-      scores(af2, T2, accp);
+      score_tile<DP>(af2, T2, accp, D, lane);
       float ds[4][ST];
 #pragma unroll
       for (int nt = 0; nt < ST; ++nt) {
-        const int col = nt * 16 + (lane & 15);
+        const int col = nt * 16 + frag_row(lane);
         const float s_lse = ROLE == ROLE_K ? sm.lse[buf][col] : 0.f;
         const float s_del = ROLE == ROLE_K ? sm.del[buf][col] : 0.f;
 #pragma unroll
@@ -326,66 +261,50 @@ DEVINL void attn_loop(const Args& a, Smem<DP>& sm, int bid, int head) {
               kept[r][nt] ? __expf(fmaf(a.scale, acc[nt][r], -lse)) : 0.f;
           ds[r][nt] = (a.scale * p) * (accp[nt][r] - del);
           if (ROLE == ROLE_K)
-            P[((lane >> 4) * 4 + r) * PL + col] = (__bf16)p;
+            P[acc_row(lane, r) * PL + col] = (__bf16)p;
         }
       }
-      if (ROLE == ROLE_K) image_times(T2, accA);      // dV += P^T dO
+      if (ROLE == ROLE_K)
+        image_times_tile<DP>(P, T2, accA, D, lane);   // dV += P^T dO
 #pragma unroll
       for (int nt = 0; nt < ST; ++nt)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          P[((lane >> 4) * 4 + r) * PL + nt * 16 + (lane & 15)] =
+          P[acc_row(lane, r) * PL + nt * 16 + frag_row(lane)] =
               (__bf16)ds[r][nt];
-      if (ROLE == ROLE_K) image_times(T1, accB);      // dK += dS^T Q
-      else image_times(T1, accA);                     // dQ += dS K
+      if (ROLE == ROLE_K)
+        image_times_tile<DP>(P, T1, accB, D, lane);   // dK += dS^T Q
+      else
+        image_times_tile<DP>(P, T1, accA, D, lane);   // dQ += dS K
     }
-
-    if (more) stash(buf ^ 1);
-    __syncthreads();
-  }
+  });
 
   // ---- epilogue. Every wave is past the loop's last barrier, so the stream
   // buffers are idle: wave w parks its tile in rows 16w.. of T1[0].
-  __bf16* R = sm.T1[0] + wave * 16 * XL;
-  auto park_store = [&](const f32x4 (&acc)[NT], const float (&mul)[4],
-                        __bf16* dst) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      if (nt * 16 < D) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          R[((lane >> 4) * 4 + r) * XL + nt * 16 + (lane & 15)] =
-              (__bf16)(acc[nt][r] * mul[r]);
-      }
-    }
-    wave_lds_sync();
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-      const int p = lane + WAVE * i;
-      const int row = row0 + p / PPR, c = (p % PPR) * 8;
-      if (row < own_end && c < D)
-        st_piece<VEC>(dst + hd, row, c, D, rs,
-                      *(const bf16x8*)&R[(p / PPR) * XL + c]);
-    }
+  __bf16* R = sm.T1[0] + wave * 16 * G::XL;
+  float mul[4] = {1.f, 1.f, 1.f, 1.f};
+  auto store = [&](const f32x4 (&acc)[NT], __bf16* dst) {
+    park_store<DP, VEC>(acc, R, dst + hd, row0, own_end, D, rs, lane,
+                        [&](float v, int r, const __bf16*) {
+                          return v * mul[r];
+                        });
     wave_lds_sync();                // R is rewritten by the next tile
   };
-
-  float mul[4] = {1.f, 1.f, 1.f, 1.f};
   if (ROLE == FWD) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float l = row_sum16(run_l[r]);
       mul[r] = l > 0.f ? 1.f / l : 0.f;
-      const int row = row0 + (lane >> 4) * 4 + r;
-      if ((lane & 15) == 0 && o_ok[r])
+      const int row = row0 + acc_row(lane, r);
+      if (frag_row(lane) == 0 && o_ok[r])
         a.lse_out[side + row] = l > 0.f ? run_m[r] + __logf(l) : NEG;
     }
-    park_store(accA, mul, a.out);
+    store(accA, a.out);
   } else if (ROLE == ROLE_Q) {
-    park_store(accA, mul, a.dq);
+    store(accA, a.dq);
   } else {
-    park_store(accA, mul, a.dv);
-    park_store(accB, mul, a.dk);
+    store(accA, a.dv);
+    store(accB, a.dk);
   }
 }
 
@@ -466,8 +385,6 @@ __global__ __launch_bounds__(SCAN) void bag_tiles_kernel(
   if (tid == SCAN - 1) pre[B] = run;     // its run ends at B: the total
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 template <int DP, bool VEC>
 void launch_fwd_dp(const Args& a, hipStream_t stream) {
   const dim3 grid((unsigned)bag_attention_max_tiles(a.n, a.B), a.H);
@@ -487,16 +404,6 @@ void launch_bwd_dp(const Args& a, hipStream_t stream) {
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
-
-#define BAG_ATTN_DISPATCH(FN, ...)                                         \
-  do {                                                                     \
-    if (D <= 64) {                                                         \
-      if (vec) FN<64, true>(__VA_ARGS__); else FN<64, false>(__VA_ARGS__); \
-    } else {                                                               \
-      if (vec) FN<128, true>(__VA_ARGS__);                                 \
-      else FN<128, false>(__VA_ARGS__);                                    \
-    }                                                                      \
-  } while (0)
 
 // offsets, kv_offsets int64 [B+1] -> qpre, kpre int32 [B+1]. B >= 1.
 void launch_bag_attention_tiles(const long* offsets, const long* kv_offsets,
@@ -523,7 +430,9 @@ void launch_bag_attention_fwd(const void* q, const void* k, const void* v,
   a.scale = scale; a.causal = causal;
   const bool vec = (D & 7) == 0 && aligned16(q) && aligned16(k) &&
                    aligned16(v) && aligned16(out);
-  BAG_ATTN_DISPATCH(launch_fwd_dp, a, stream);
+  dispatch_dp_vec<kBagAttnMaxD>(D, vec, [&](auto c) {
+    launch_fwd_dp<decltype(c)::dp, decltype(c)::vec>(a, stream);
+  });
 }
 
 // out, lse: the forward's; dout [n,H,D] bf16 contiguous; delta fp32 [H,n]
@@ -553,5 +462,7 @@ void launch_bag_attention_bwd(const void* q, const void* k, const void* v,
   const bool vec = (D & 7) == 0 && aligned16(q) && aligned16(k) &&
                    aligned16(v) && aligned16(dout) && aligned16(dq) &&
                    aligned16(dk) && aligned16(dv);
-  BAG_ATTN_DISPATCH(launch_bwd_dp, a, stream);
+  dispatch_dp_vec<kBagAttnMaxD>(D, vec, [&](auto c) {
+    launch_bwd_dp<decltype(c)::dp, decltype(c)::vec>(a, stream);
+  });
 }

@@ -16,8 +16,8 @@
 // word is ~index. "Beats" is one unsigned compare and the score comes back
 // exactly. Key 0 is "no item": a real -inf has the high word 0x007fffff.
 //
-// One loop (score_loop) serves three roles. As in sampled_softmax.hip a block
-// of 4 waves OWNS 64 queries — wave w the rows 16w..16w+15, as MFMA A
+// One loop (score_loop) serves three roles. On the scheme of mfma_stream.h a
+// block of 4 waves OWNS 64 queries — wave w the rows 16w..16w+15, as MFMA A
 // fragments in registers — and STREAMS item tiles of 64 rows through two
 // row-major LDS buffers of stride DP + 8, the bias riding along: the global
 // loads of tile i+1 are issued before the arithmetic of tile i and written to
@@ -73,9 +73,6 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr int WAVES = 4;
-constexpr int OWN = WAVES * 16;   // owned queries per block
-constexpr int TILE = 64;          // streamed items per tile
 constexpr int CAP = 128;          // candidate keys per owned row
 constexpr int KROW = CAP + 2;     // buffer row stride: rows 4 banks apart
 enum { TOPK = 0, TRUE_SCORE = 1, COUNT = 2 };
@@ -160,24 +157,17 @@ DEVINL u64 compact_row(S& sm, int row, int k, int lane) {
 template <int ROLE, int DP, bool VEC>
 DEVINL void score_loop(const Args& a, Smem<DP, ROLE == TOPK>& sm, int own_tile,
                        int t_begin, int t_end, int split) {
-  constexpr int XL = DP + 8;
-  constexpr int KS = DP / 32;       // K steps of the scores
-  constexpr int PIECES = TILE * (DP / 8) / (WAVES * WAVE);   // == KS
-  constexpr int PPR = DP / 8;       // 16-byte pieces per image row
-  constexpr int NT = TILE / 16;
+  typedef Stream<DP> G;
+  constexpr int NT = ST;
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wave = tid >> 6;
   const int D = a.D, V = a.V, k = a.k;
   const int row0 = own_tile * OWN + wave * 16;
-  const int arow = row0 + (lane & 15);      // this lane's A-fragment row
-  const int kq = (lane >> 4) << 3;          // its K offset inside a step
-  const int lrow0 = wave * 16 + (lane >> 4) * 4;   // first accumulator row
+  const int lrow0 = wave * 16 + acc_row(lane, 0);   // first accumulator row
 
-  bf16x8 af[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
-    af[ks] = ld_piece<VEC>(a.q, arow, a.B, ks * 32 + kq, D, D);
+  bf16x8 af[G::KS];
+  load_owned<DP, VEC>(af, a.q, row0, a.B, D, D, lane);
 
   bool o_ok[4];
 #pragma unroll
@@ -195,27 +185,18 @@ DEVINL void score_loop(const Args& a, Smem<DP, ROLE == TOPK>& sm, int own_tile,
   };
 
   // streamed tile t: global -> registers (fetch), registers -> LDS (stash)
-  bf16x8 pre[PIECES];
+  bf16x8 pre[G::PIECES];
   float pre_bias = 0.f;
   auto fetch = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-      const int p = tid + WAVES * WAVE * i;
-      const long j = item(t, p / PPR);
-      pre[i] = ld_piece<VEC>(a.w, j < 0 ? 0 : (int)j, j < 0 ? 0 : V,
-                             (p % PPR) * 8, D, D);
-    }
+    tile_fetch<DP, VEC>(pre, a.w, D, D, tid,
+                        [&](int trow) { return item(t, trow); });
     if (tid < TILE) {
       const long j = item(t, tid);
       pre_bias = a.bias && j >= 0 ? a.bias[j] : 0.f;
     }
   };
   auto stash = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-      const int p = tid + WAVES * WAVE * i;
-      *(bf16x8*)&sm.T[buf][(p / PPR) * XL + (p % PPR) * 8] = pre[i];
-    }
+    tile_stash<DP>(sm.T[buf], pre, tid);
     if (tid < TILE) sm.bias[buf][tid] = pre_bias;
   };
 
@@ -241,28 +222,16 @@ DEVINL void score_loop(const Args& a, Smem<DP, ROLE == TOPK>& sm, int own_tile,
     const int buf = (t - t_begin) & 1;
     const bool more = t + 1 < t_end;    // block-uniform
     if (more) fetch(t + 1);
-    const __bf16* T = sm.T[buf];
 
     f32x4 acc[NT] = {};
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      if (ks * 32 < D) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-          const bf16x8 b = *(const bf16x8*)&T[(nt * 16 + (lane & 15)) * XL +
-                                              ks * 32 + kq];
-          acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks], b, acc[nt],
-                                                            0, 0, 0);
-        }
-      }
-    }
+    score_tile<DP>(af, sm.T[buf], acc, D, lane);
 
     float s_bias[NT];
     unsigned s_col[NT];             // < 2^31 + 64: no wrap
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-      s_bias[nt] = sm.bias[buf][nt * 16 + (lane & 15)];
-      s_col[nt] = (unsigned)t * TILE + nt * 16 + (lane & 15);
+      s_bias[nt] = sm.bias[buf][nt * 16 + frag_row(lane)];
+      s_col[nt] = (unsigned)t * TILE + nt * 16 + frag_row(lane);
     }
 
     if constexpr (ROLE == TOPK) {
@@ -327,7 +296,7 @@ DEVINL void score_loop(const Args& a, Smem<DP, ROLE == TOPK>& sm, int own_tile,
       for (int r = 0; r < 4; ++r) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-          if (nt == wave && (lane & 15) == (lane >> 4) * 4 + r && o_ok[r]) {
+          if (nt == wave && frag_row(lane) == acc_row(lane, r) && o_ok[r]) {
             const int b = own_tile * OWN + lrow0 + r;
             a.true_key[b] =
                 make_key(acc[nt][r] + s_bias[nt], (unsigned)a.labels[b]);
@@ -399,28 +368,15 @@ __global__ __launch_bounds__(WAVES * WAVE) void dot_rank_finish_kernel(
   rank[b] = n;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-template <int ROLE, int DP, bool VEC>
-void launch_score(const Args& a, int nsplit, hipStream_t stream) {
-  const dim3 grid((a.B + OWN - 1) / OWN, nsplit), block(WAVES * WAVE);
-  hipLaunchKernelGGL((dot_score_kernel<ROLE, DP, VEC>), grid, block, 0, stream,
-                     a);
-}
-
 template <int ROLE>
-void dispatch_score(const Args& a, int nsplit, hipStream_t stream) {
+void launch_score(const Args& a, int nsplit, hipStream_t stream) {
   const bool vec = (a.D & 7) == 0 && aligned16(a.q) && aligned16(a.w);
-  if (a.D <= 64) {
-    if (vec) launch_score<ROLE, 64, true>(a, nsplit, stream);
-    else launch_score<ROLE, 64, false>(a, nsplit, stream);
-  } else if (a.D <= 128) {
-    if (vec) launch_score<ROLE, 128, true>(a, nsplit, stream);
-    else launch_score<ROLE, 128, false>(a, nsplit, stream);
-  } else {
-    if (vec) launch_score<ROLE, 256, true>(a, nsplit, stream);
-    else launch_score<ROLE, 256, false>(a, nsplit, stream);
-  }
+  const dim3 grid((a.B + OWN - 1) / OWN, nsplit), block(WAVES * WAVE);
+  dispatch_dp_vec<kDotTopkMaxD>(a.D, vec, [&](auto c) {
+    hipLaunchKernelGGL(
+        (dot_score_kernel<ROLE, decltype(c)::dp, decltype(c)::vec>), grid,
+        block, 0, stream, a);
+  });
 }
 
 Args make_args(const void* q, const void* w, const float* bias, int B, int V,
@@ -439,21 +395,11 @@ Args make_args(const void* q, const void* w, const float* bias, int B, int V,
 #pragma clang attribute pop
 #endif
 
-// the rule of sampled_softmax_nsplit: clamp(256 / ceil(B/64), 1, ceil(V/64))
-int dot_topk_nsplit(long B, long V) {
-  const long own = (B + OWN - 1) / OWN;
-  const long n = 256 / own;
-  return dot_topk_splits(B, V, n < 1 ? 1 : n);
-}
+// the split rule of mfma_stream.h
+int dot_topk_nsplit(long B, long V) { return dot_topk_splits(B, V, 0); }
 
-// then the fewest splits of that many tiles each (no split is empty)
 int dot_topk_splits(long B, long V, long splits) {
-  if (splits == 0) return dot_topk_nsplit(B, V);
-  const long ntiles = (V + TILE - 1) / TILE;
-  long n = splits < 1 ? 1 : splits > ntiles ? ntiles : splits;
-  n = n > 65535 ? 65535 : n;        // the grid's y limit
-  const long per = (ntiles + n - 1) / n;
-  return (int)((ntiles + per - 1) / per);
+  return stream_splits(V, splits == 0 ? stream_default_splits(B) : splits);
 }
 
 // q [B,D], w [V,D] bf16 contiguous; bias fp32 [V] or null; ws int64
@@ -466,7 +412,7 @@ void launch_dot_topk(const void* q, const void* w, const float* bias,
   Args a = make_args(q, w, bias, B, V, D, nsplit);
   a.k = k;
   a.ws = (u64*)ws;
-  dispatch_score<TOPK>(a, nsplit, stream);
+  launch_score<TOPK>(a, nsplit, stream);
   hipLaunchKernelGGL(dot_topk_merge_kernel, dim3((B + WAVES - 1) / WAVES),
                      dim3(WAVES * WAVE), 0, stream, a.ws, nsplit, B, k, values,
                      indices);
@@ -482,8 +428,8 @@ void launch_dot_rank(const void* q, const void* w, const float* bias,
   a.labels = labels;
   a.true_key = (u64*)true_key;
   a.ws = (u64*)ws;
-  dispatch_score<TRUE_SCORE>(a, 1, stream);
-  dispatch_score<COUNT>(a, nsplit, stream);
+  launch_score<TRUE_SCORE>(a, 1, stream);
+  launch_score<COUNT>(a, nsplit, stream);
   hipLaunchKernelGGL(dot_rank_finish_kernel,
                      dim3((B + WAVES * WAVE - 1) / (WAVES * WAVE)),
                      dim3(WAVES * WAVE), 0, stream, a.ws, nsplit, B, rank);

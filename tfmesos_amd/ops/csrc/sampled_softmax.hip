@@ -11,7 +11,9 @@
 //   dh = P W_samp + q w_true, dw_samp = P^T H, dw_true = q h,
 //   dsamp_adj = column sums of P, dtrue_adj = q.
 //
-// One loop (pair_loop) serves the forward and both backward products. A
+// One loop (pair_loop) serves the forward and both backward products, on the
+// scheme of mfma_stream.h (geometry, leaf helpers, dispatch and split rule
+// from there; the loop's pieces are written out here, see that file). A
 // block of 4 waves OWNS 64 rows of one set — wave w the rows 16w..16w+15, as
 // MFMA A fragments loaded once from global memory into registers — and
 // STREAMS the other set through LDS in tiles of 64 rows, row-major [row][d]
@@ -57,12 +59,6 @@ namespace {
 
 #include "mfma_stream.h"
 
-constexpr int WAVES = 4;
-constexpr int OWN = WAVES * 16;   // owned rows per block
-constexpr int TILE = 64;          // streamed rows per tile
-constexpr int PL = TILE + 8;      // P image row stride
-constexpr float NEG = -1e30f;     // "no kept score yet": finite, so that the
-                                  // merge of two empty halves is exp(0) * 0
 enum { FWD = 0, ROLE_H = 1, ROLE_W = 2 };
 
 struct Args {
@@ -417,8 +413,6 @@ __global__ __launch_bounds__(WAVES * WAVE) void sampled_softmax_finish_kernel(
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 template <int DP, bool VEC>
 void launch_fwd_dp(const Args& a, int nsplit, hipStream_t stream) {
   const dim3 grid((a.B + OWN - 1) / OWN, nsplit), block(WAVES * WAVE);
@@ -439,28 +433,10 @@ void launch_bwd_dp(const Args& a, hipStream_t stream) {
 #pragma clang attribute pop
 #endif
 
-// clamp(256 / ceil(B/64), 1, ceil(S/64)), then the fewest splits of that
-// many tiles each (no split is empty)
+// the split rule of mfma_stream.h with its default number of splits
 int sampled_softmax_nsplit(long B, long S) {
-  const long own = (B + OWN - 1) / OWN, ntiles = (S + TILE - 1) / TILE;
-  long n = 256 / own;
-  n = n < 1 ? 1 : n > ntiles ? ntiles : n;
-  const long per = (ntiles + n - 1) / n;
-  return (int)((ntiles + per - 1) / per);
+  return stream_splits(S, stream_default_splits(B));
 }
-
-#define SAMPLED_DISPATCH(FN, ...)                                         \
-  do {                                                                    \
-    if (D <= 64) {                                                        \
-      if (vec) FN<64, true>(__VA_ARGS__); else FN<64, false>(__VA_ARGS__); \
-    } else if (D <= 128) {                                                \
-      if (vec) FN<128, true>(__VA_ARGS__);                                \
-      else FN<128, false>(__VA_ARGS__);                                   \
-    } else {                                                              \
-      if (vec) FN<256, true>(__VA_ARGS__);                                \
-      else FN<256, false>(__VA_ARGS__);                                   \
-    }                                                                     \
-  } while (0)
 
 // h, w_true [B,D], w_samp [S,D] bf16 contiguous; true_adj [B], samp_adj [S]
 // fp32 or null; labels [B], sampled [S] int64, both or neither null;
@@ -481,7 +457,9 @@ void launch_sampled_softmax_fwd(const void* h, const void* w_true,
   const int ntiles = (S + TILE - 1) / TILE;
   a.tiles_per_split = (ntiles + nsplit - 1) / nsplit;
   const bool vec = (D & 7) == 0 && aligned16(h) && aligned16(w_samp);
-  SAMPLED_DISPATCH(launch_fwd_dp, a, nsplit, stream);
+  dispatch_dp_vec<kSampledMaxD>(D, vec, [&](auto c) {
+    launch_fwd_dp<decltype(c)::dp, decltype(c)::vec>(a, nsplit, stream);
+  });
   hipLaunchKernelGGL(sampled_softmax_finish_kernel,
                      dim3((B + FIN_EX - 1) / FIN_EX), dim3(WAVES * WAVE), 0,
                      stream, a.h, a.w_true, true_adj, ws, nsplit, B, D, lse,
@@ -512,5 +490,7 @@ void launch_sampled_softmax_bwd(const void* h, const void* w_true,
   const bool vec = (D & 7) == 0 && aligned16(h) && aligned16(w_true) &&
                    aligned16(w_samp) && aligned16(dh) && aligned16(dw_true) &&
                    aligned16(dw_samp);
-  SAMPLED_DISPATCH(launch_bwd_dp, a, stream);
+  dispatch_dp_vec<kSampledMaxD>(D, vec, [&](auto c) {
+    launch_bwd_dp<decltype(c)::dp, decltype(c)::vec>(a, stream);
+  });
 }

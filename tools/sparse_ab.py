@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """A/B of one kernel family between this tree and a second built tree:
 same bits, same speed. --suite sparse (the default) is described first;
---suite bn, the batch-norm kernels, at the end.
+--suite bn, the batch-norm kernels, and --suite stream at the end.
 
     python tools/sparse_ab.py /path/to/other/tree --out profiles/NAME.txt
 
@@ -47,6 +47,23 @@ Inception-stage and grouped cases, by the rule above. End to end:
 --dump-outputs compared for equality. The other tree runs the same-bits
 cases and the benchmark twice: a case or array that it does not reproduce
 itself (a kernel with a data race) is reported as such and not compared.
+
+--suite stream, the kernels on the scheme of csrc/mfma_stream.h, through the
+extension's bindings, on seeded normal rows. Same bits: sampled softmax
+forward and backward (lse, loss, dh, dw_true, dw_samp, dtrue_adj, dsamp_adj)
+at the (B, S) of tests/test_sampled_softmax_gpu.py for every D of ST_D and
+at the shapes of tools/sampledbench.py, with and without ids and
+adjustments, and one case with misaligned bases; bag attention forward and
+backward (out, lse, dq, dk, dv) over the bags of
+tests/test_bag_attention_gpu.py, self, causal, cross and k is v, H in
+{1, 3}, one misaligned case, and the workloads of tools/attnbench.py;
+dot_topk and dot_rank (values, indices, ranks) at the shapes of
+tests/test_dot_topk_gpu.py and tools/topkbench.py, with and without bias,
+splits default and 1. Same speed: forward and forward+backward (dot_topk
+and dot_rank) at the three benches' shapes. The other tree runs the
+same-bits cases twice, as for bn. End to end: ``bench.py`` (mnist) on both
+trees; it runs none of these kernels and shows only that the shared
+extension still builds to the same thing.
 """
 
 import argparse
@@ -353,6 +370,197 @@ def bn_child_time(ops, out, min_s):
         json.dump(times, fh)
 
 
+# ---------------------------------------------------------- stream children
+
+ST_D = [7, 8, 64, 65, 72, 128, 129, 200, 256]
+SS_UNIT = [(5, 130), (67, 65), (130, 5), (1, 64)]                   # B, S
+SS_BENCH = [(4096, 4096, 128), (1024, 8192, 64), (8192, 1024, 256)]
+QL, KL = (0, 1, 63, 64, 65, 130), (5, 0, 64, 130, 1, 65)    # bag lengths
+TK_UNIT = [(5, 130, 1), (5, 130, 10), (67, 65, 64), (1, 64, 64), (130, 5, 5),
+           (3, 387, 64)]                                            # B, V, k
+TK_RANDOM = [(67, 1000, 72, 10), (67, 1000, 200, 10), (67, 1000, 128, 64)]
+TK_BENCH = [(1024, 1 << 20, 64, 10, False), (1024, 1 << 20, 128, 64, False),
+            (64, 1 << 22, 64, 10, False), (1024, 1 << 20, 64, 10, True)]
+
+
+def bf16_rows(gen, *shape):
+    return (torch.randn(*shape, device=DEV, generator=gen)
+            * shape[-1] ** -0.25).to(torch.bfloat16)
+
+
+def misaligned(t):
+    """A contiguous copy of t one element into its storage."""
+    buf = torch.zeros(t.numel() + 1, dtype=t.dtype, device=t.device)
+    return buf[1:].view_as(t).copy_(t)
+
+
+def ss_inputs(gen, B, S, D, id_range):
+    h, wt, ws = bf16_rows(gen, B, D), bf16_rows(gen, B, D), bf16_rows(gen, S, D)
+    ta = torch.randn(B, device=DEV, generator=gen)
+    sa = torch.randn(S, device=DEV, generator=gen)
+    labels = torch.randint(0, id_range, (B,), device=DEV, generator=gen)
+    sampled = torch.randint(0, id_range, (S,), device=DEV, generator=gen)
+    g = torch.rand(B, device=DEV, generator=gen) + 0.5
+    return [h, wt, ws, ta, sa, labels, sampled], g
+
+
+def ss_run(ext, x, g, plain=False):
+    """-> [lse, loss, dh, dw_true, dw_samp, dtrue_adj, dsamp_adj]"""
+    if plain:
+        x = x[:3] + [None] * 4
+    loss, lse = ext.sampled_softmax_fwd(*x)
+    return [lse, loss] + list(ext.sampled_softmax_bwd(
+        x[0], x[1], x[2], x[4], x[5], x[6], lse, loss, g))
+
+
+def offsets_of(lens):
+    lens = torch.as_tensor(lens, dtype=torch.int64)
+    return torch.cat([lens.new_zeros(1), lens.cumsum(0)]).to(DEV)
+
+
+def attn_inputs(gen, qlens, klens, H, D):
+    """klens None: self-attention over the query bags."""
+    n = int(sum(qlens))
+    m = n if klens is None else int(sum(klens))
+    rows = lambda r: torch.randn(r, H, D, device=DEV, generator=gen).to(  # noqa: E731
+        torch.bfloat16)
+    qoff = offsets_of(qlens)
+    return [rows(n), rows(m), rows(m), rows(n), qoff,
+            qoff if klens is None else offsets_of(klens)]
+
+
+def attn_run(ext, x, causal, bwd=True):
+    """-> [out, lse, dq, dk, dv]"""
+    q, k, v, dout, qoff, koff = x
+    scale = q.shape[-1] ** -0.5
+    out, lse = ext.bag_attention_fwd(q, k, v, qoff, koff, causal, scale)
+    if not bwd:
+        return [out, lse]
+    return [out, lse] + list(ext.bag_attention_bwd(
+        q, k, v, out, lse, dout, qoff, koff, causal, scale))
+
+
+def attn_bench_inputs(name):
+    """The workloads of tools/attnbench.py: (inputs, causal)."""
+    B, causal, target = dict(self=(256, False, False),
+                             causal=(256, True, False),
+                             target=(2048, False, True))[name]
+    klens = torch.randint(8, 193, (B,),
+                          generator=torch.Generator().manual_seed(0))
+    gen = torch.Generator(device=DEV).manual_seed(1)
+    if target:
+        return attn_inputs(gen, torch.ones_like(klens), klens, 4, 64), causal
+    return attn_inputs(gen, klens, None, 4, 64), causal
+
+
+def tk_inputs(gen, B, V, D, ascending=False):
+    q, w = bf16_rows(gen, B, D), bf16_rows(gen, V, D)
+    bias = torch.randn(V, device=DEV, generator=gen)
+    labels = torch.randint(0, V, (B,), device=DEV, generator=gen)
+    if ascending:       # query 0's row is compacted at every tile
+        perm = torch.argsort(w.float() @ q[0].float() + bias)
+        w, bias = w[perm].contiguous(), bias[perm].contiguous()
+    return q, w, bias, labels
+
+
+def tk_run(ops, x, k, bias, splits):
+    """-> [values, indices, ranks]"""
+    q, w, b, labels = x
+    b = b if bias else None
+    return list(ops.dot_topk(q, w, k, b, splits)) + [
+        ops.dot_rank(q, w, labels, b, splits)]
+
+
+def stream_child_check(ops, out):
+    ext = ops._ext()
+    saved = {}
+
+    def put(tag, tensors):
+        saved[tag] = [keep(t) for t in tensors]
+
+    # sampled softmax: lse, loss, dh, dw_true, dw_samp, dtrue_adj, dsamp_adj
+    for B, S, D in [(B, S, D) for B, S in SS_UNIT for D in ST_D] + SS_BENCH:
+        gen = torch.Generator(device=DEV).manual_seed(4000 + 7 * B + 3 * S + D)
+        x, g = ss_inputs(gen, B, S, D, S if (B, S) in SS_UNIT else 8 * S)
+        for plain in (False, True):
+            put("sampled %dx%dx%d %s" % (B, S, D, "plain" if plain else "ids+adj"),
+                ss_run(ext, x, g, plain))
+    gen = torch.Generator(device=DEV).manual_seed(4001)
+    x, g = ss_inputs(gen, 67, 65, 8, 65)
+    put("sampled 67x65x8 misaligned",
+        ss_run(ext, [misaligned(t) for t in x[:3]] + x[3:], g))
+
+    # bag attention: out, lse, dq, dk, dv
+    for D in (7, 8, 64, 65, 72, 128):
+        for H in (1, 3):
+            gen = torch.Generator(device=DEV).manual_seed(5000 + 10 * D + H)
+            x = attn_inputs(gen, QL, None, H, D)
+            for causal in (False, True):
+                put("attention self D=%d H=%d causal=%d" % (D, H, causal),
+                    attn_run(ext, x, causal))
+            x = attn_inputs(gen, QL, KL, H, D)
+            put("attention cross D=%d H=%d" % (D, H), attn_run(ext, x, False))
+            x[2] = x[1]
+            put("attention k is v D=%d H=%d" % (D, H), attn_run(ext, x, False))
+    gen = torch.Generator(device=DEV).manual_seed(5001)
+    x = attn_inputs(gen, QL, KL, 3, 8)
+    put("attention cross D=8 H=3 misaligned",
+        attn_run(ext, [misaligned(t) for t in x[:4]] + x[4:], False))
+    for name in ("self", "causal", "target"):
+        x, causal = attn_bench_inputs(name)
+        put("attention bench " + name, attn_run(ext, x, causal))
+
+    # dot_topk, dot_rank: values, indices, ranks
+    cases = [(B, V, D, k, False) for B, V, k in TK_UNIT for D in ST_D
+             if D != 200] + [c + (False,) for c in TK_RANDOM] + TK_BENCH
+    for B, V, D, k, asc in cases:
+        gen = torch.Generator(device=DEV).manual_seed(6000 + 7 * B + 3 * V + D)
+        x = tk_inputs(gen, B, V, D, asc)
+        for bias in (True, False):
+            for splits in (None, 1):
+                put("topk %dx%dx%dx%d%s bias=%d splits=%s"
+                    % (B, V, D, k, "a" if asc else "", bias, splits),
+                    tk_run(ops, x, k, bias, splits))
+        del x
+    torch.cuda.synchronize()
+    torch.save(saved, out)
+
+
+def stream_child_time(ops, out, min_s):
+    ext = ops._ext()
+    times = {}
+
+    def measure(rows):
+        for label, fn in rows:
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            times[label] = window(fn, min_s)
+
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    for B, S, D in SS_BENCH:
+        x, g = ss_inputs(gen, B, S, D, 8 * S)
+        name = "sampled %dx%dx%d " % (B, S, D)
+        measure([(name + "fwd", lambda: ext.sampled_softmax_fwd(*x)),
+                 (name + "fwd+bwd", lambda: ss_run(ext, x, g))])
+    for wl in ("self", "causal", "target"):
+        x, causal = attn_bench_inputs(wl)
+        name = "attention %s " % wl
+        measure([(name + "fwd", lambda: attn_run(ext, x, causal, False)),
+                 (name + "fwd+bwd", lambda: attn_run(ext, x, causal))])
+    for B, V, D, k, asc in TK_BENCH:
+        x = tk_inputs(gen, B, V, D, asc)
+        name = "%dx%dx%dx%d%s " % (B, V, D, k, "a" if asc else "")
+        measure([(name + "dot_topk",
+                  lambda: ops.dot_topk(x[0], x[1], k, x[2])),
+                 (name + "dot_rank",
+                  lambda: ops.dot_rank(x[0], x[1], x[3], x[2]))])
+        del x
+        torch.cuda.empty_cache()
+    with open(out, "w") as fh:
+        json.dump(times, fh)
+
+
 def child(args):
     sys.path.insert(0, args.tree)
     from tfmesos_amd import ops
@@ -375,6 +583,10 @@ def nmf_bench(args, dump):
 def inception_bench(args, dump):
     return ["--workload", "inception", "--steps", "20", "--warmup", "5",
             "--dump-outputs", dump]
+
+
+def mnist_bench(args, dump):
+    return ["--steps", "2000", "--warmup", "200"]
 
 
 def same_dumps(tmp):
@@ -406,6 +618,12 @@ SUITES = {
         title="batch-norm kernels", check=bn_child_check, time=bn_child_time,
         big=BN_BIG, speed="Inception-stage layers and block-A groups, relu",
         bench=inception_bench, dumps=same_dumps, repeat=True),
+    "stream": dict(
+        title="streamed-tile MFMA kernels (sampled softmax, bag attention, "
+              "dot_topk / dot_rank)",
+        check=stream_child_check, time=stream_child_time, big=BIG,
+        speed="the shapes of sampledbench.py, attnbench.py and topkbench.py",
+        bench=mnist_bench, repeat=True),
 }
 
 
@@ -446,7 +664,7 @@ def main():
     ap.add_argument("--label", default=None,
                     help="what the other tree is, for the report's first "
                          "line (default: its path)")
-    ap.add_argument("--suite", choices=["sparse", "bn"], default="sparse")
+    ap.add_argument("--suite", choices=sorted(SUITES), default="sparse")
     ap.add_argument("--child", choices=["check", "time"], default=None)
     ap.add_argument("--child-out", default=None)
     args = ap.parse_args()
