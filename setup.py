@@ -34,6 +34,7 @@ sources = [
     os.path.join(CSRC, "interaction.hip"),
     os.path.join(CSRC, "sampled_softmax.hip"),
     os.path.join(CSRC, "retrieval.hip"),
+    os.path.join(CSRC, "dot_softmax.hip"),
     os.path.join(CSRC, "bag_attention.hip"),
 ]
 

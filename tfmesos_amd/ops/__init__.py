@@ -34,7 +34,9 @@ sampled_softmax_loss; in-batch negatives), forward and backward. A bag read
 as a sequence: bag_attention, fused softmax attention inside each CSR bag
 (target attention, self-attention, causal), forward and backward. Evaluating
 and serving over the whole vocabulary: dot_topk and dot_rank (TF's top_k /
-in_top_k over q @ w.T + bias), fused scoring and selection.
+in_top_k over q @ w.T + bias), fused scoring and selection; and training
+over it: dot_softmax_loss, the exact softmax cross-entropy with nothing
+[B, V]-sized in memory, forward and backward.
 """
 
 import collections
@@ -850,6 +852,105 @@ def dot_rank(q, w, labels, bias=None, splits=None):
     t = s.gather(1, labels[:, None])
     before = torch.arange(V)[None, :] < labels[:, None]
     return ((s > t) | ((s == t) & before)).sum(1)
+
+
+def dot_softmax_nsplit(B, V, splits=None):
+    """The splits of the streamed set ``dot_softmax_loss`` runs with on the
+    GPU, ``(forward, backward-q, backward-w)``: a function of (B, V, splits)
+    only. The forward and the backward's role Q stream the items, role W
+    streams the examples."""
+    return tuple(_ext().dot_softmax_nsplit(int(B), int(V), int(splits or 0)))
+
+
+def _dot_softmax_terms(q, w, bias, labels, g, lse, loss):
+    """fp32 P' [B, V]: g exp(s - lse), the label's entry g expm1(-loss),
+    rows of ignored examples 0."""
+    live = labels >= 0
+    g = torch.where(live, g, torch.zeros_like(g))
+    p = g[:, None] * torch.exp(_dot_scores(q, w, bias) - lse[:, None])
+    return p.scatter(1, labels.clamp(min=0)[:, None],
+                     (g * torch.expm1(-loss))[:, None])
+
+
+class _DotSoftmaxFn(torch.autograd.Function):
+    """Differentiable dot_softmax_loss. GPU: csrc/dot_softmax.hip; CPU: the
+    same op in plain fp32 torch."""
+
+    @staticmethod
+    def forward(ctx, q, w, bias, labels, splits):
+        ctx.splits = splits
+        if q.is_cuda:
+            loss, lse = _ext().dot_softmax_fwd(q, w, labels, bias, splits)
+        else:
+            s = _dot_scores(q, w, bias)
+            lse = torch.logsumexp(s, 1)
+            t = s.gather(1, labels.clamp(min=0)[:, None])[:, 0]
+            loss = torch.where(labels >= 0, lse - t, torch.zeros_like(lse))
+        ctx.save_for_backward(q, w, bias, labels, lse, loss)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        q, w, bias, labels, lse, loss = ctx.saved_tensors
+        g = g.float().contiguous()
+        if q.is_cuda:
+            dq, dw, dbias = _ext().dot_softmax_bwd(q, w, labels, bias, lse,
+                                                   loss, g, ctx.splits)
+        else:
+            p = _dot_softmax_terms(q, w, bias, labels, g, lse, loss)
+            dq = (p @ w.float()).to(q.dtype)
+            dw = (p.t() @ q.float()).to(w.dtype)
+            dbias = p.sum(0)
+        return dq, dw, None if bias is None else dbias, None, None
+
+
+def dot_softmax_loss(q, w, labels, bias=None, splits=None):
+    """Softmax cross-entropy of each query against a whole vocabulary,
+    without [B, V] logits in memory (TF's
+    ``sparse_softmax_cross_entropy_with_logits`` over ``q @ w.T + bias``):
+    the loss a model evaluated with ``dot_rank`` trains with.
+
+    q, w, bias and the score s[b, j] are those of ``dot_topk`` (a bias of
+    -inf masks an item out; a label's own item must not be masked). labels
+    is int64 [B]: an item in [0, V), or -1 for an ignored example (a padding
+    position), whose loss is +0.0 and which contributes to no gradient.
+    Other values are rejected on the CPU; the GPU path does not sync, and a
+    label outside the range is memory-safe and leaves that example's loss
+    meaningless (``dot_rank``'s rule). NaNs are outside the contract.
+
+        loss[b] = logsumexp_j s[b, j] - s[b, labels[b]]
+
+    Returns loss, fp32 [B]; dot products, exp, log and sums are fp32,
+    max-subtracted. Differentiable in q and w (bf16 gradients, accumulated
+    in fp32 and rounded once; on the GPU the probabilities are rounded to
+    bf16 on their way into the MFMA operand) and in bias (fp32). The
+    gradient of w is one dense [V, D] tensor with the label term in it: it
+    feeds a dense store, or ``push(arange(V), ...)``, unchanged. The label's
+    entry of ``softmax - onehot`` is formed as ``g expm1(-loss)``.
+
+    1 <= D <= 256 (DOT_TOPK_MAX_D), 1 <= V < 2**31, any B and base
+    alignment. ``splits=None`` lets the launcher choose how many blocks
+    share a streamed set (``dot_softmax_nsplit``); an integer forces the
+    number for the forward and both backward roles, each clamped to its own
+    tile count. Every count stays within the same error bounds; the bits
+    depend on it. GPU: csrc/dot_softmax.hip - MFMA scores in the forward and
+    in both backward products, fp32 partial tiles and a reduce where a role
+    splits, no atomics, bit-reproducible for a given (shape, splits), no
+    host sync. CPU: the [B, V] scores in fp32.
+    """
+    name = "dot_softmax_loss"
+    _, _, _, nsplit = _retrieval_args(name, q, w, bias, splits)
+    B, V = q.shape[0], w.shape[0]
+    if labels.dtype != torch.int64 or labels.shape != (B,):
+        raise ValueError("%s: labels [B] must be int64" % name)
+    if B == 0:
+        return torch.empty(0, device=q.device)
+    if not q.is_cuda and (int(labels.min()) < -1 or int(labels.max()) >= V):
+        raise ValueError("%s: labels must be -1 or lie in [0, %d)" % (name, V))
+    return _DotSoftmaxFn.apply(
+        q.contiguous(), w.contiguous(),
+        None if bias is None else bias.contiguous(), labels.contiguous(),
+        nsplit)
 
 
 # ------------------------------------------------- attention over CSR bags

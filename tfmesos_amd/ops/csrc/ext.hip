@@ -15,6 +15,7 @@
 #include "pool.h"
 #include "sampled_softmax.h"
 #include "retrieval.h"
+#include "dot_softmax.h"
 #include "bag_attention.h"
 #include "softmax_xent.h"
 
@@ -987,6 +988,69 @@ torch::Tensor dot_rank(torch::Tensor q, torch::Tensor w, torch::Tensor labels,
                   (long*)rank.data_ptr<int64_t>(), (int)B, (int)V, (int)D,
                   nsplit, cur_stream());
   return rank;
+}
+
+// Full-softmax loss over a vocabulary (dot_softmax.hip): q, w, bias as for
+// dot_topk (kDotSoftmaxMaxD == kDotTopkMaxD), labels int64 [B] with -1 for an
+// ignored example. splits == 0 lets dot_softmax_plan choose.
+static_assert(kDotSoftmaxMaxD == kDotTopkMaxD, "retrieval_check bounds D");
+
+std::tuple<long, long, long> dot_softmax_nsplit(long B, long V, long splits) {
+  TORCH_CHECK(B >= 1 && V >= 1 && splits >= 0,
+              "dot_softmax_nsplit: need B, V >= 1 and splits >= 0");
+  const DotSoftmaxPlan p = dot_softmax_plan(B, V, splits);
+  return {p.fwd, p.bwd_q, p.bwd_w};
+}
+
+// -> (loss [B], lse [B]) fp32
+std::tuple<torch::Tensor, torch::Tensor> dot_softmax_fwd(
+    torch::Tensor q, torch::Tensor w, torch::Tensor labels, OptTensor bias,
+    long splits) {
+  const char* op = "dot_softmax_fwd";
+  retrieval_check(op, q, w, splits);
+  const long B = q.size(0), V = w.size(0), D = q.size(1);
+  TORCH_CHECK(i64_vec(labels) && labels.size(0) == B,
+              op, ": labels [B] must be int64 on GPU");
+  const int nsplit = dot_softmax_plan(B, V, splits).fwd;
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto ws = torch::empty({2L * nsplit * B}, f32), s_true = torch::empty({B}, f32);
+  auto loss = torch::empty({B}, f32), lse = torch::empty({B}, f32);
+  launch_dot_softmax_fwd(q.data_ptr(), w.data_ptr(), ssm_f32(op, bias, V),
+                         (const long*)labels.data_ptr<int64_t>(),
+                         ws.data_ptr<float>(), s_true.data_ptr<float>(),
+                         lse.data_ptr<float>(), loss.data_ptr<float>(), (int)B,
+                         (int)V, (int)D, nsplit, cur_stream());
+  return {loss, lse};
+}
+
+// g = dloss fp32 [B] -> (dq, dw bf16; dbias fp32)
+std::vector<torch::Tensor> dot_softmax_bwd(
+    torch::Tensor q, torch::Tensor w, torch::Tensor labels, OptTensor bias,
+    torch::Tensor lse, torch::Tensor loss, torch::Tensor g, long splits) {
+  const char* op = "dot_softmax_bwd";
+  retrieval_check(op, q, w, splits);
+  const long B = q.size(0), V = w.size(0), D = q.size(1);
+  TORCH_CHECK(i64_vec(labels) && labels.size(0) == B,
+              op, ": labels [B] must be int64 on GPU");
+  const DotSoftmaxPlan p = dot_softmax_plan(B, V, splits);
+  const long tq = (B + 63) / 64, tw = (V + 63) / 64;
+  TORCH_CHECK(tq * p.bwd_q + tw * p.bwd_w <= INT_MAX,
+              op, ": too many blocks for one launch; lower splits");
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto dq = torch::empty_like(q), dw = torch::empty_like(w);
+  auto dbias = torch::empty({V}, f32);
+  // fp32 partial tiles of a role that splits its streamed set
+  auto part_q = torch::empty({p.bwd_q > 1 ? p.bwd_q * B * D : 0}, f32);
+  auto part_w = torch::empty({p.bwd_w > 1 ? p.bwd_w * V * D : 0}, f32);
+  auto part_b = torch::empty({p.bwd_w > 1 ? p.bwd_w * V : 0}, f32);
+  launch_dot_softmax_bwd(
+      q.data_ptr(), w.data_ptr(), ssm_f32(op, bias, V),
+      (const long*)labels.data_ptr<int64_t>(), ssm_f32(op, lse, B),
+      ssm_f32(op, loss, B), ssm_f32(op, g, B), part_q.data_ptr<float>(),
+      part_w.data_ptr<float>(), part_b.data_ptr<float>(), dq.data_ptr(),
+      dw.data_ptr(), dbias.data_ptr<float>(), (int)B, (int)V, (int)D, p.bwd_q,
+      p.bwd_w, cur_stream());
+  return {dq, dw, dbias};
 }
 
 // Attention over CSR bags (bag_attention.hip): q [n,H,D], k, v [m,H,D] bf16,
@@ -1964,6 +2028,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dot_rank", &dot_rank, py::arg("q"), py::arg("w"), py::arg("labels"),
         py::arg("bias"), py::arg("splits"));
   m.def("dot_topk_nsplit", &dot_topk_nsplit, py::arg("B"), py::arg("V"));
+  m.def("dot_softmax_fwd", &dot_softmax_fwd, py::arg("q"), py::arg("w"),
+        py::arg("labels"), py::arg("bias"), py::arg("splits"));
+  m.def("dot_softmax_bwd", &dot_softmax_bwd, py::arg("q"), py::arg("w"),
+        py::arg("labels"), py::arg("bias"), py::arg("lse"), py::arg("loss"),
+        py::arg("g"), py::arg("splits"));
+  m.def("dot_softmax_nsplit", &dot_softmax_nsplit, py::arg("B"), py::arg("V"),
+        py::arg("splits"));
   m.def("bag_attention_fwd", &bag_attention_fwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("offsets"), py::arg("kv_offsets"),
         py::arg("causal"), py::arg("scale"));
