@@ -36,6 +36,7 @@ sources = [
     os.path.join(CSRC, "retrieval.hip"),
     os.path.join(CSRC, "dot_softmax.hip"),
     os.path.join(CSRC, "bag_attention.hip"),
+    os.path.join(CSRC, "norm.hip"),
 ]
 
 setup(

@@ -36,7 +36,10 @@ as a sequence: bag_attention, fused softmax attention inside each CSR bag
 and serving over the whole vocabulary: dot_topk and dot_rank (TF's top_k /
 in_top_k over q @ w.T + bias), fused scoring and selection; and training
 over it: dot_softmax_loss, the exact softmax cross-entropy with nothing
-[B, V]-sized in memory, forward and backward.
+[B, V]-sized in memory, forward and backward. The norms of a transformer
+block over the packed rows: layer_norm, LayerNorm / RMSNorm with the residual
+add fused in, forward and backward (layer_norm_fwd, layer_norm_bwd,
+layer_norm_plan).
 """
 
 import collections
@@ -1098,6 +1101,240 @@ def bag_attention(q, k, v, offsets, kv_offsets=None, causal=False,
     return _BagAttentionFn.apply(q.contiguous(), k.contiguous(),
                                  v.contiguous(), offsets, kv_offsets,
                                  bool(causal), scale)
+
+
+# -------------------------------------- residual add + LayerNorm / RMSNorm
+
+LAYER_NORM_MAX_D = 1024        # csrc/norm.h: kNormMaxD
+_NORM_PARAM_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def _norm_check(name, x, weight, residual=None, bias=None, like="x"):
+    """Validates the rows and the parameters; returns (n, D)."""
+    if x.dtype != torch.bfloat16 or x.dim() < 1 or not x.is_contiguous():
+        raise ValueError("%s: %s must be contiguous bf16 [..., D], got %s %s"
+                         % (name, like, x.dtype, tuple(x.shape)))
+    D = x.shape[-1]
+    if not 1 <= D <= LAYER_NORM_MAX_D:
+        raise ValueError("%s: D = %d, need 1 <= D <= %d"
+                         % (name, D, LAYER_NORM_MAX_D))
+    n = x.numel() // D
+    if n >= 2 ** 31:
+        raise ValueError("%s: n = %d rows, need n < 2**31" % (name, n))
+    if residual is not None and (
+            residual.dtype != x.dtype or residual.shape != x.shape
+            or not residual.is_contiguous()):
+        raise ValueError("%s: the rows beside %s must be contiguous bf16 of "
+                         "its shape %s, got %s %s" % (name, like, tuple(x.shape),
+                                            residual.dtype,
+                                            tuple(residual.shape)))
+    for p in (weight, bias):
+        if p is not None and (p.dtype not in _NORM_PARAM_DTYPES
+                              or p.shape != (D,) or not p.is_contiguous()):
+            raise ValueError("%s: weight and bias must be contiguous fp32 or "
+                             "bf16 [%d], got %s %s"
+                             % (name, D, p.dtype, tuple(p.shape)))
+    return n, D
+
+
+def _norm_blocks(name, blocks):
+    if blocks is None:
+        return 0
+    if (isinstance(blocks, bool) or not isinstance(blocks, int)
+            or not 1 <= blocks < 2 ** 31):
+        raise ValueError("%s: blocks must be an int in [1, 2**31) or None, "
+                         "got %r" % (name, blocks))
+    return blocks
+
+
+def layer_norm_plan(n, D, blocks=None):
+    """``(lanes_per_row, rows_per_block, blocks)`` of ``ops.layer_norm`` on
+    the GPU for n rows of width D: the lanes that share a row, the rows a
+    256-thread block holds, and the blocks of the backward launch (each
+    writes one partial row of dweight / dbias). ``blocks=None`` is the
+    default rule, one block a row group up to 1024; an integer is clamped to
+    that range. The launcher's own host function: a function of (n, D,
+    blocks) only."""
+    return tuple(_ext().layer_norm_plan(
+        int(n), int(D), _norm_blocks("layer_norm_plan", blocks)))
+
+
+def _norm_fwd_rows(x, weight, bias, eps, residual, rms, y_out=None,
+                   s_out=None):
+    """layer_norm_fwd on validated rows [n, D]."""
+    if x.is_cuda:
+        return _ext().layer_norm_fwd(x, weight, bias, eps, residual, rms,
+                                     y_out, s_out)
+    s = x if residual is None else (x.float() + residual.float()).to(
+        torch.bfloat16)
+    sf = s.float()
+    mean = sf.new_zeros(sf.shape[0]) if rms else sf.mean(1)
+    d = sf - mean[:, None]
+    rstd = 1.0 / torch.sqrt((d * d).mean(1) + eps)
+    y = d * rstd[:, None]
+    if weight is not None:
+        y = y * weight.float()
+    if bias is not None:
+        y = y + bias.float()
+    y = y.to(torch.bfloat16)
+    return (y if y_out is None else y_out.copy_(y),
+            s if s_out is None else s_out.copy_(s), mean, rstd)
+
+
+def _norm_bwd_rows(dy, s, mean, rstd, weight, rms, ds, bias_dtype, blocks,
+                   dx_out=None):
+    """layer_norm_bwd on validated rows [n, D]; bias_dtype None: no dbias."""
+    if s.is_cuda:
+        return _ext().layer_norm_bwd(
+            dy, s, mean, rstd, weight, rms, ds,
+            0 if bias_dtype is None else 1 if bias_dtype == torch.float32
+            else 2, blocks, dx_out)
+    xh = (s.float() - mean[:, None]) * rstd[:, None]
+    dyf = dy.float()
+    g = dyf if weight is None else dyf * weight.float()
+    t = g - xh * (g * xh).mean(1, keepdim=True)
+    if not rms:
+        t = t - g.mean(1, keepdim=True)
+    dx = rstd[:, None] * t
+    if ds is not None:
+        dx = dx + ds.float()
+    dx = dx.to(torch.bfloat16)
+    return (dx if dx_out is None else dx_out.copy_(dx),
+            None if weight is None else (dyf * xh).sum(0).to(weight.dtype),
+            None if bias_dtype is None else dyf.sum(0).to(bias_dtype))
+
+
+def layer_norm_fwd(x, weight, bias, eps, residual, rms, out=None):
+    """The forward of ``layer_norm`` without autograd: ``(y, s, mean,
+    rstd)``, y and s shaped like x (s is x itself without a residual), mean
+    and rstd fp32 [n] (mean zeros with rms). ``out=(y, s)`` names tensors to
+    write y and s into (s None without a residual)."""
+    name = "layer_norm_fwd"
+    n, D = _norm_check(name, x, weight, residual, bias)
+    y_out, s_out = (None, None) if out is None else out
+    for o in (y_out, s_out):
+        if o is not None:
+            _norm_check(name, x, None, o)
+    if s_out is not None and residual is None:
+        raise ValueError("%s: s is x without a residual and takes no out"
+                         % name)
+    rows = lambda t: None if t is None else t.view(n, D)  # noqa: E731
+    y, s, mean, rstd = _norm_fwd_rows(
+        x.view(n, D), weight, bias, float(eps), rows(residual), bool(rms),
+        rows(y_out), rows(s_out))
+    return y.view(x.shape), s.view(x.shape), mean, rstd
+
+
+def layer_norm_bwd(dy, s, mean, rstd, weight, rms, ds=None, has_bias=True,
+                   blocks=None, out=None):
+    """The backward of ``layer_norm`` without autograd: ``(dx, dweight,
+    dbias)`` from the forward's s, mean and rstd. ds, the gradient arriving
+    through the returned s, is added in fp32. dweight is None without a
+    weight and has its dtype; ``has_bias`` is False (dbias None), True (dbias
+    in weight's dtype, fp32 without a weight) or the dtype dbias is to have.
+    ``out`` names a tensor to write dx into."""
+    name = "layer_norm_bwd"
+    n, D = _norm_check(name, s, weight, like="s")
+    for t in (dy, ds, out):
+        if t is not None:
+            _norm_check(name, s, None, t, like="s")
+    nblocks = _norm_blocks(name, blocks)
+    for t in (mean, rstd):
+        if t.dtype != torch.float32 or t.shape != (n,):
+            raise ValueError("%s: mean and rstd must be fp32 [%d]" % (name, n))
+    if has_bias is True:
+        has_bias = torch.float32 if weight is None else weight.dtype
+    if has_bias and has_bias not in _NORM_PARAM_DTYPES:
+        raise ValueError("%s: has_bias must be a bool, torch.float32 or "
+                         "torch.bfloat16, got %r" % (name, has_bias))
+    rows = lambda t: None if t is None else t.view(n, D)  # noqa: E731
+    dx, dw, db = _norm_bwd_rows(
+        rows(dy), rows(s), mean.contiguous(), rstd.contiguous(), weight,
+        bool(rms), rows(ds), has_bias or None, nblocks, rows(out))
+    return dx.view(s.shape), dw, db
+
+
+class _LayerNormFn(torch.autograd.Function):
+    """Differentiable layer_norm on validated rows [n, D]. GPU:
+    csrc/norm.hip; CPU: the same op in plain fp32 torch. Returns (y, s) with
+    a residual, y without."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, eps, rms, blocks):
+        y, s, mean, rstd = _norm_fwd_rows(x, weight, bias, eps, residual, rms)
+        ctx.save_for_backward(s, mean, rstd, weight)
+        ctx.rms, ctx.blocks = rms, blocks
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        ctx.set_materialize_grads(False)
+        return y if residual is None else (y, s)
+
+    @staticmethod
+    def backward(ctx, dy, ds=None):
+        s, mean, rstd, weight = ctx.saved_tensors
+        if dy is None and ds is None:
+            return (None,) * 7
+        dy = torch.zeros_like(s) if dy is None else dy.contiguous()
+        dx, dw, db = _norm_bwd_rows(
+            dy, s, mean, rstd, weight, ctx.rms,
+            None if ds is None else ds.contiguous(), ctx.bias_dtype,
+            ctx.blocks)
+        return (dx, dw, db, dx if ctx.needs_input_grad[3] else None, None,
+                None, None)
+
+
+def layer_norm(x, weight=None, bias=None, eps=1e-5, residual=None, rms=False,
+               blocks=None):
+    """LayerNorm or RMSNorm of packed rows with the residual add fused in:
+    the two norms of a transformer block (SASRec, BST) over the rows that
+    ``bag_attention`` and ``linear`` work on.
+
+    x is bf16 [..., D], contiguous; the leading dims are n rows. residual is
+    None or bf16 of x's shape. weight and bias are [D], fp32 (the store's
+    masters) or bf16 (its shadows), each optional: without a weight the
+    scale is 1 and no dweight is formed.
+
+        s    = bf16(fp32(x) + fp32(residual))     (s = x without a residual)
+        mean = sum(s) / D, var = sum((s - mean)^2) / D   (two-pass)
+        rstd = 1 / sqrt(var + eps)
+        y    = bf16(weight (s - mean) rstd + bias)
+
+    ``rms=True`` does not subtract the mean: rstd = 1 / sqrt(sum(s^2) / D +
+    eps). Everything after the add is defined on the rounded s, so
+    ``layer_norm(x, residual=r)`` equals ``layer_norm(bf16(x + r))`` bit for
+    bit. Returns y, or ``(y, s)`` with a residual: the normalised rows and
+    the new residual stream.
+
+    Differentiable in x, residual, weight and bias. With g = dy weight and
+    xh = (s - mean) rstd, dx = rstd (g - mean_D(g) - xh mean_D(g xh)) plus
+    the gradient arriving through s, in fp32, rounded to bf16 once; with rms
+    the mean_D(g) term is absent. x and residual get the same tensor.
+    dweight = sum_rows dy xh and dbias = sum_rows dy are summed in fp32 and
+    rounded once to the parameter's dtype.
+
+    1 <= D <= 1024 (LAYER_NORM_MAX_D), n < 2**31, any base alignment; n == 0
+    returns empty tensors. GPU: csrc/norm.hip - one pass over the rows in
+    each direction, the row in registers, 8 to 64 lanes a row by its width;
+    the backward's blocks (``layer_norm_plan``; ``blocks=`` forces the
+    number) each write one fp32 partial row of dweight / dbias and a
+    finishing kernel adds them in block order: no atomics, bit-reproducible
+    for a given (n, D, blocks), no host sync. CPU: plain fp32 torch.
+    """
+    name = "layer_norm"
+    n, D = _norm_check(name, x, weight, residual, bias)
+    for t in (weight, bias, residual):
+        if t is not None and t.device != x.device:
+            raise ValueError("%s: every tensor must be on x's device" % name)
+    blocks = _norm_blocks(name, blocks)
+    if x.dim() == 2:
+        return _LayerNormFn.apply(x, weight, bias, residual, float(eps),
+                                  bool(rms), blocks)
+    out = _LayerNormFn.apply(
+        x.view(n, D), weight, bias,
+        None if residual is None else residual.view(n, D), float(eps),
+        bool(rms), blocks)
+    if residual is None:
+        return out.view(x.shape)
+    return out[0].view(x.shape), out[1].view(x.shape)
 
 
 # ----------------------------------------------- row-sharded table routing

@@ -17,6 +17,7 @@
 #include "retrieval.h"
 #include "dot_softmax.h"
 #include "bag_attention.h"
+#include "norm.h"
 #include "softmax_xent.h"
 
 namespace {
@@ -1153,6 +1154,124 @@ std::vector<torch::Tensor> bag_attention_bwd(
   return {dq, dk, dv};
 }
 
+// Residual-add + LayerNorm / RMSNorm (norm.hip) over rows [n, D] bf16.
+static bool norm_rows(const torch::Tensor& t) {
+  return t.is_cuda() && t.dim() == 2 && t.is_contiguous() &&
+         t.scalar_type() == torch::kBFloat16;
+}
+
+// A [D] parameter, fp32 or bf16, or none: its pointer and whether it is bf16.
+static const void* norm_param(const char* op, const OptTensor& t, long D,
+                              int* is_bf16) {
+  *is_bf16 = 0;
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->dim() == 1 && t->size(0) == D &&
+              t->is_contiguous() &&
+              (t->scalar_type() == torch::kFloat32 ||
+               t->scalar_type() == torch::kBFloat16),
+              op, ": weight and bias must be contiguous fp32 or bf16 [D] on GPU");
+  *is_bf16 = t->scalar_type() == torch::kBFloat16;
+  return t->data_ptr();
+}
+
+// An output the caller supplies (a view into its own storage), or a new one.
+static torch::Tensor norm_out(const char* op, const OptTensor& out,
+                              const torch::Tensor& like) {
+  if (!out.has_value()) return torch::empty_like(like);
+  TORCH_CHECK(norm_rows(*out) && out->sizes() == like.sizes(),
+              op, ": an output must be contiguous bf16 [n,D] on GPU like x");
+  return *out;
+}
+
+static void norm_dims(const char* op, const torch::Tensor& x) {
+  TORCH_CHECK(norm_rows(x), op, ": rows must be contiguous bf16 [n,D] on GPU");
+  TORCH_CHECK(x.size(1) >= 1 && x.size(1) <= kNormMaxD && x.size(0) < (1L << 31),
+              op, ": need 1 <= D <= ", kNormMaxD, " and n < 2^31");
+}
+
+std::tuple<long, long, long> layer_norm_plan(long n, long D, long blocks) {
+  TORCH_CHECK(n >= 0 && n < (1L << 31) && D >= 1 && D <= kNormMaxD &&
+              blocks >= 0,
+              "layer_norm_plan: need 0 <= n < 2^31, 1 <= D <= ", kNormMaxD,
+              " and blocks >= 0");
+  const NormPlan p = norm_plan(n, (int)D, blocks);
+  return {p.lanes, p.rows, p.blocks};
+}
+
+// -> (y, s, mean, rstd); s is x itself without a residual
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+layer_norm_fwd(torch::Tensor x, OptTensor weight, OptTensor bias, double eps,
+               OptTensor residual, bool rms, OptTensor y_out, OptTensor s_out) {
+  const char* op = "layer_norm_fwd";
+  norm_dims(op, x);
+  const long n = x.size(0), D = x.size(1);
+  TORCH_CHECK(!residual.has_value() ||
+              (norm_rows(*residual) && residual->sizes() == x.sizes()),
+              op, ": residual must be contiguous bf16 [n,D] on GPU like x");
+  TORCH_CHECK(residual.has_value() || !s_out.has_value(),
+              op, ": s is x without a residual and takes no output");
+  NormFwdArgs a = {};
+  a.w = norm_param(op, weight, D, &a.w_bf16);
+  a.b = norm_param(op, bias, D, &a.b_bf16);
+  auto y = norm_out(op, y_out, x);
+  auto s = residual.has_value() ? norm_out(op, s_out, x) : x;
+  auto f32 = x.options().dtype(torch::kFloat32);
+  auto mean = torch::empty({n}, f32), rstd = torch::empty({n}, f32);
+  if (n == 0) return {y, s, mean, rstd};
+  a.x = x.data_ptr(); a.y = y.data_ptr();
+  if (residual.has_value()) {
+    a.res = residual->data_ptr(); a.s_out = s.data_ptr();
+  }
+  a.mean = mean.data_ptr<float>(); a.rstd = rstd.data_ptr<float>();
+  a.n = n; a.D = (int)D; a.eps = (float)eps; a.rms = rms;
+  launch_norm_fwd(a, cur_stream());
+  return {y, s, mean, rstd};
+}
+
+// dbias: 0 none, 1 fp32, 2 bf16 -> (dx, dweight or None, dbias or None);
+// dweight has weight's dtype
+std::tuple<torch::Tensor, OptTensor, OptTensor> layer_norm_bwd(
+    torch::Tensor dy, torch::Tensor s, torch::Tensor mean, torch::Tensor rstd,
+    OptTensor weight, bool rms, OptTensor ds, long dbias, long blocks,
+    OptTensor dx_out) {
+  const char* op = "layer_norm_bwd";
+  norm_dims(op, s);
+  const long n = s.size(0), D = s.size(1);
+  TORCH_CHECK(norm_rows(dy) && dy.sizes() == s.sizes() &&
+              (!ds.has_value() ||
+               (norm_rows(*ds) && ds->sizes() == s.sizes())),
+              op, ": dy and ds must be contiguous bf16 [n,D] on GPU like s");
+  TORCH_CHECK(dbias >= 0 && dbias <= 2 && blocks >= 0,
+              op, ": dbias must be 0, 1 or 2 and blocks >= 0");
+  NormBwdArgs a = {};
+  a.w = norm_param(op, weight, D, &a.w_bf16);
+  a.mean = ssm_f32(op, mean, n); a.rstd = ssm_f32(op, rstd, n);
+  auto dx = norm_out(op, dx_out, s);
+  auto f32 = s.options().dtype(torch::kFloat32);
+  OptTensor dw, db;
+  if (weight.has_value()) dw = torch::empty_like(*weight);
+  if (dbias) db = torch::empty({D}, dbias == 2 ? s.options() : f32);
+  if (n == 0) {
+    if (dw.has_value()) dw->zero_();
+    if (db.has_value()) db->zero_();
+    return {dx, dw, db};
+  }
+  const NormPlan p = norm_plan(n, (int)D, blocks);
+  torch::Tensor part;
+  if (dw.has_value() || db.has_value()) {
+    part = torch::empty({p.blocks, 2, D}, f32);
+    a.part = part.data_ptr<float>();
+    if (dw.has_value()) a.dw = dw->data_ptr();
+    if (db.has_value()) a.db = db->data_ptr();
+    a.dw_bf16 = a.w_bf16; a.db_bf16 = dbias == 2;
+  }
+  a.dy = dy.data_ptr(); a.s = s.data_ptr(); a.dx = dx.data_ptr();
+  if (ds.has_value()) a.ds = ds->data_ptr();
+  a.n = n; a.D = (int)D; a.rms = rms; a.blocks = p.blocks;
+  launch_norm_bwd(a, cur_stream());
+  return {dx, dw, db};
+}
+
 torch::Tensor colsum(torch::Tensor x, torch::Tensor out) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
               x.is_contiguous() && x.dim() == 2, "colsum: bf16 [M,N]");
@@ -2042,4 +2161,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("dout"),
         py::arg("offsets"), py::arg("kv_offsets"), py::arg("causal"),
         py::arg("scale"));
+  m.def("layer_norm_fwd", &layer_norm_fwd, py::arg("x"), py::arg("weight"),
+        py::arg("bias"), py::arg("eps"), py::arg("residual"), py::arg("rms"),
+        py::arg("y_out") = py::none(), py::arg("s_out") = py::none());
+  m.def("layer_norm_bwd", &layer_norm_bwd, py::arg("dy"), py::arg("s"),
+        py::arg("mean"), py::arg("rstd"), py::arg("weight"), py::arg("rms"),
+        py::arg("ds"), py::arg("dbias"), py::arg("blocks"),
+        py::arg("dx_out") = py::none());
+  m.def("layer_norm_plan", &layer_norm_plan, py::arg("n"), py::arg("D"),
+        py::arg("blocks"));
 }
